@@ -7,11 +7,18 @@ with fp32 accumulation and fp32 master weights; for N > 1 ranks the flat fp32 gr
 (RCCL over xGMI) before Adam.  Weak scaling: 256 clips per GPU per step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload audio|hybrid|cvae] [--dtype bf16|fp32]
-                    [--grad-dtype bf16|fp32] [--no-cpu-baseline] [--no-roofline] [--no-extras] [--graph]
+                    [--grad-dtype bf16|fp32] [--graph] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-roofline] [--no-extras]]
 N > 1 runs one process per GPU under torch.distributed.run; `python bench.py --gpus N` outside torchrun starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process (nothing touches the GPU in the
 parent), relays rank 0's JSON line and exits with the child's status.  Rank 0 prints ONE JSON line.
-Besides the headline (BASELINE config[1]), the default run times three more workloads on the same mel stage and
+A plain run does only what the headline needs: setup, W warm-up steps, K timed steps, the result line.
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/<name>.npy, float32 / float64; the inputs
+are seeded, so two builds run with the same arguments can be compared array by array).
+`--full` adds everything else the benchmark measures: the per-kind roofline of the step's kernels (untimed
+calibration steps, then HIP events around the dominant kernel's launches in the last timed steps), the host cores'
+CPU baseline, and the extras.
+Besides the headline (BASELINE config[1]), a `--full` run times three more workloads on the same mel stage and
 reports them under "extras" (never as `value`): the headline in fp32 (the parity precision), the hybrid ConvVAE
 with 384-d lyrics (config[2]) and the genre-conditioned ConditionalVAE (config[3]), each bs=256 per GPU; the
 K-Means fit of config[3]/[4]'s clustering scale (N = 100 000 x 128, k = 10, n_init = 10) beside sklearn's on the
@@ -321,6 +328,26 @@ def cpu_baseline(batch=256, steps=5, warmup=2):
                       f"{warmup} warm-up steps ({dt:.1f} s: mel {t_mel:.1f} s, VAE {t_vae:.1f} s)"}
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of each flat parameter-sized array (fixed, seeded positions)
+
+
+def dump_outputs(path, B, mel, trainer, model, sums):
+    """What the last timed step handed its caller, as path/<name>.npy (float32, the loss sums float64; 42 MB at
+    B = 256): the device loss sums Trainer.step returned, the z-scored mel batch the step consumed (the mel stage's
+    output), the step's recon / mu / logvar (/ recon_text), and the same DUMP_SAMPLE seeded positions of the flat
+    gradient and of the Adam-updated parameters."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss_sums": sums, "audio": mel.audio, **trainer._cache[B]["out"]}
+    flat = {"grad": trainer.gflat.detach(), "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])}
+    n = flat["grad"].numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    for k, v in flat.items():
+        arrays[f"{k}_sample"] = v[torch.from_numpy(idx).to(v.device)]
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        np.save(os.path.join(path, f"{k}.npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
@@ -385,10 +412,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--workload", choices=["audio", "hybrid", "cvae"], default="audio")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32 / hybrid / CVAE extra lines")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the kernel roofline, the extras and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extras")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--grad-dtype", choices=["bf16", "fp32"], default="fp32",
                     help="gradient all-reduce wire for N > 1 (default fp32, the reference's numerics; bf16 halves the "
                          "xGMI bytes and is reported as the labelled `headline_bf16_wire` extra, DESIGN.md §7)")
@@ -398,6 +429,8 @@ def main():
                     help="replay the step as one HIP graph (N = 1 only; measured 12%% slower on ROCm 7: the graph "
                          "executor serialises the weight-gradient stream's branch, see DESIGN.md)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_roofline = args.no_extras = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus))
@@ -496,6 +529,8 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, B, mel, trainer, model, sums)
     live, probe_note = None, None
     if dominant:
         try:

@@ -1,8 +1,11 @@
-# bench.py (no CPU baseline) + rocprofv3 kernel trace of a short bench run -> gpurun_out/prof
-cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out && R=$GRAFT_REPO_ROOT
+# bench.py --full (no CPU baseline) + rocprofv3 kernel trace of a short bench run -> $OUT/prof (OUT: results
+# directory, default out/ in the repository)
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/out}
+cd $R && mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 python bench.py --no-cpu-baseline > gpurun_out/bench.log 2>&1; rc=$?; echo "bench rc=$rc"
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench.log 2>&1; rc=$?; echo "bench rc=$rc"
 [ $rc -eq 0 ] || exit $rc
 cd /tmp
-rm -rf $R/gpurun_out/prof
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof -o run --output-format csv -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline > $R/gpurun_out/prof.log 2>&1; rc=$?; echo "prof rc=$rc"
+rm -rf $OUT/prof
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-roofline > $OUT/prof.log 2>&1; rc=$?; echo "prof rc=$rc"
