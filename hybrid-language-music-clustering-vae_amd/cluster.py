@@ -25,6 +25,9 @@ seeds from one RandomState stream; a seeding consumes a data-independent number 
 its own restarts see the same random numbers as in a single process.  One ``all_gather_object`` of (restart,
 labels, inertia, centres, n_iter) at the end feeds sklearn's sequential best-of rule in restart order, so the
 result is bit-identical for any world size.
+
+DBSCAN (end of this file) replaces ``sklearn.cluster.DBSCAN(eps, min_samples=5).fit_predict`` and the eps search at
+src/Convolutional_VAE.py:347-374,382: fp64 MFMA neighbourhoods and union-find labelling on the device.
 """
 from __future__ import annotations
 
@@ -362,3 +365,140 @@ class KMeans:
         L.check(L.lib().hlmc_km_assign(L.stream(), Xd.data_ptr(), n, d, C_.data_ptr(), self.n_clusters,
                                        labels.data_ptr(), None, None))
         return labels.cpu().numpy()
+
+
+# ====================================================================================== DBSCAN
+_DBSCAN_WORKSPACE_CAP = 24 << 30   # bytes of bit-packed adjacency held at once by a sweep (17 radii at n = 100,000)
+_DBSCAN_MAX_RADII = 32             # radii per hlmc_dbscan_neighbors call
+
+
+def _radius_sq(eps):
+    """sklearn's float32 radius-neighbours path squares the radius in float32: the threshold the float64 squared
+    distances are compared with is float64(float32(float32(eps) * float32(eps))), not eps ** 2."""
+    e = np.float32(eps)
+    return float(np.float32(e * e))
+
+
+def _dbscan_device_x(X, device):
+    if torch.is_tensor(X):
+        dev = torch.device(device) if device is not None else (X.device if X.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        Xd = X.detach().to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        Xd = torch.as_tensor(np.asarray(X, dtype=np.float32), device=dev).contiguous()
+    if Xd.dim() != 2 or Xd.shape[0] < 1 or Xd.shape[1] < 1:
+        raise ValueError("X must be 2-D [n_samples, n_features] with at least one row and one column")
+    return Xd
+
+
+def _dbscan_pass(Xd, eps_list, min_samples, workspace_cap=None):
+    """One neighbourhood pass per chunk of radii (as many as the workspace cap holds, at most 32), then the
+    labelling pass per radius.  Yields (index, labels int64 [n], core mask bool [n], borderline pairs) in the
+    order of eps_list; nothing is copied back before a chunk's last launch is queued."""
+    if min_samples < 1:
+        raise ValueError("min_samples must be >= 1")
+    eps_list = [float(e) for e in eps_list]
+    if not eps_list or any(not e > 0.0 for e in eps_list):
+        raise ValueError("eps must be > 0")
+    lib = L.lib()
+    n, d = Xd.shape
+    dev = Xd.device
+    cap = _DBSCAN_WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    if int(lib.hlmc_dbscan_workspace(n, 1)) <= 0:
+        raise ValueError(f"DBSCAN: n_samples={n} is outside the supported range [1, 262144]")
+    chunk = min(_DBSCAN_MAX_RADII, len(eps_list))   # the most radii whose adjacencies fit under the cap (>= 1)
+    while chunk > 1 and int(lib.hlmc_dbscan_workspace(n, chunk)) > cap:
+        chunk -= 1
+    ws_bytes = int(lib.hlmc_dbscan_workspace(n, chunk))
+    with torch.cuda.device(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        for c0 in range(0, len(eps_list), chunk):
+            grp = eps_list[c0:c0 + chunk]
+            E = len(grp)
+            r = (C.c_double * E)(*[_radius_sq(e) for e in grp])
+            counts = torch.empty(E, n, dtype=torch.int32, device=dev)
+            border = torch.empty(E, dtype=torch.int64, device=dev)
+            labels = torch.empty(E, n, dtype=torch.int32, device=dev)
+            core = torch.empty(E, n, dtype=torch.uint8, device=dev)
+            # a chunk's workspace size was computed for `chunk` radii; a shorter last chunk fits in it
+            L.check(lib.hlmc_dbscan_neighbors(L.stream(), Xd.data_ptr(), n, d, r, E, counts.data_ptr(),
+                                              border.data_ptr(), ws.data_ptr(), ws_bytes), "hlmc_dbscan_neighbors")
+            for e in range(E):
+                L.check(lib.hlmc_dbscan_labels(L.stream(), n, E, e, int(min_samples), counts.data_ptr(), ws.data_ptr(),
+                                               ws_bytes, labels[e].data_ptr(), core[e].data_ptr(), None),
+                        "hlmc_dbscan_labels")
+            lab_h = labels.cpu().numpy().astype(np.int64)
+            core_h = core.cpu().numpy().astype(bool)
+            border_h = border.cpu().numpy()
+            for e in range(E):
+                yield c0 + e, lab_h[e], core_h[e], int(border_h[e])
+
+
+class DBSCAN:
+    """sklearn.cluster.DBSCAN for float32 data with the neighbourhoods and the labelling on the GPU
+    (src/Convolutional_VAE.py:353-354,382: ``DBSCAN(eps=eps, min_samples=5).fit_predict(latent_matrix)``).
+
+    ``labels_`` and ``core_sample_indices_`` are bit-identical to sklearn 1.7's brute-force float32 path:
+    i and j are neighbours iff max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) <= float32(eps)^2 (squared in float32),
+    evaluated in float64; clusters are numbered by their smallest core index; a border point joins the
+    lowest-numbered cluster among its core neighbours.
+
+    sklearn's ``algorithm='auto'`` switches to a KD-tree (direct differences, another rounding) when
+    ``n_features <= 15``; this class always uses the brute-force arithmetic, so for d <= 15 the guarantee is
+    against ``sklearn.cluster.DBSCAN(algorithm='brute')``.
+
+    ``n_borderline_pairs_`` counts the pairs i < j whose squared distance lies within
+    4 (d + 4) 2^-53 (|x_i|^2 + |x_j|^2) of the threshold: only those could be decided differently by another
+    summation order of the dot product (sklearn's comes from a BLAS dgemm).  When it is 0 the labels equal
+    sklearn's by construction.  It is reported, never acted on.
+    """
+
+    def __init__(self, eps=0.5, *, min_samples=5, metric="euclidean", device=None):
+        if metric != "euclidean":
+            raise ValueError("only metric='euclidean' (the reference's) is implemented")
+        self.eps, self.min_samples, self.metric, self.device = eps, min_samples, metric, device
+
+    def fit(self, X, y=None, sample_weight=None):
+        if sample_weight is not None:
+            raise ValueError("sample_weight is not supported (the reference never passes it)")
+        Xd = _dbscan_device_x(X, self.device)
+        (_, labels, core, border), = _dbscan_pass(Xd, [self.eps], self.min_samples)
+        self.labels_ = labels
+        self.core_sample_indices_ = np.flatnonzero(core)
+        idx = torch.as_tensor(self.core_sample_indices_, device=Xd.device)
+        self.components_ = Xd[idx].cpu().numpy()
+        self.n_features_in_ = Xd.shape[1]
+        self.n_borderline_pairs_ = border
+        return self
+
+    def fit_predict(self, X, y=None, sample_weight=None):
+        return self.fit(X, sample_weight=sample_weight).labels_
+
+
+def dbscan_eps_sweep(X, eps_range=np.arange(3.0, 20.0, 1.0), min_samples=5, *, device=None, workspace_cap=None):
+    """The reference's DBSCAN radius search (src/Convolutional_VAE.py:347-374) with one neighbourhood pass for
+    all radii (chunked to ``workspace_cap`` bytes of adjacency).
+
+    Returns ``(best_eps, records)``.  ``records[i]`` describes ``eps_range[i]``: ``eps``, ``labels`` (int64,
+    bit-identical to ``DBSCAN(eps, min_samples).fit_predict(X)``), ``n_clusters`` (noise excluded), ``n_noise``,
+    ``n_borderline_pairs`` and ``silhouette`` (``metrics.silhouette_score(X, labels)`` with noise as a label of
+    its own, as the reference passes it; ``None`` when the radius has fewer than 2 clusters).  ``best_eps`` is
+    the first radius with the highest silhouette, or the reference's default 10.0 when no radius qualifies."""
+    from . import metrics as M
+    Xd = _dbscan_device_x(X, device)
+    eps_list = [float(e) for e in np.asarray(eps_range, dtype=np.float64).reshape(-1)]
+    records = []
+    best_eps, best_sil = 5.0, -1
+    for i, labels, core, border in _dbscan_pass(Xd, eps_list, min_samples, workspace_cap):
+        n_clusters = int(labels.max()) + 1 if labels.size else 0
+        n_noise = int((labels == -1).sum())
+        sil = None
+        if n_clusters >= 2:
+            sil = M.silhouette_score(Xd, labels)
+            if sil > best_sil:
+                best_sil, best_eps = sil, eps_list[i]
+        records.append({"eps": eps_list[i], "labels": labels, "n_clusters": n_clusters, "n_noise": n_noise,
+                        "n_borderline_pairs": border, "silhouette": sil})
+    if best_sil == -1:
+        best_eps = 10.0
+    return best_eps, records

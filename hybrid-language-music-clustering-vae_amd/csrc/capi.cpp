@@ -444,6 +444,17 @@ int hlmc_cluster_scores(void* stream, const float* X, int64_t n, int d, const in
     return metrics::cluster_scores(S(stream), X, n, d, labels, k, out2, ws, (size_t)ws_bytes);
 }
 
+// ------------------------------------------------------------------------------------ DBSCAN
+int64_t hlmc_dbscan_workspace(int64_t n, int E) { return (int64_t)dbscan::workspace(n, E); }
+int hlmc_dbscan_neighbors(void* stream, const float* X, int64_t n, int d, const double* radii_sq, int E, int32_t* counts,
+                          uint64_t* borderline, void* ws, int64_t ws_bytes) {
+    return dbscan::neighbors(S(stream), X, n, d, radii_sq, E, counts, borderline, ws, ws_bytes < 0 ? 0 : (size_t)ws_bytes);
+}
+int hlmc_dbscan_labels(void* stream, int64_t n, int E, int e, int min_samples, const int32_t* counts, void* ws,
+                       int64_t ws_bytes, int32_t* labels, uint8_t* core, int32_t* n_clusters) {
+    return dbscan::labels(S(stream), n, E, e, min_samples, counts, ws, ws_bytes < 0 ? 0 : (size_t)ws_bytes, labels, core,
+                          n_clusters);
+}
 
 // ------------------------------------------------------------------------------------ op-level entries
 // Individual GEMM-family kernels (the building blocks of hlmc_net_*), exposed for testing and reuse.

@@ -91,4 +91,14 @@ int cluster_scores(hipStream_t s, const float* X, int64_t n, int d, const int32_
                    void* ws, size_t ws_bytes);
 }  // namespace metrics
 
+// DBSCAN with sklearn's labels (dbscan.hip): one neighbourhood pass for up to 32 squared radii (bit-packed
+// adjacency in the workspace, per-row neighbour counts, borderline-pair counts), then a labelling pass per radius.
+namespace dbscan {
+size_t workspace(int64_t n, int E);
+int neighbors(hipStream_t s, const float* X, int64_t n, int d, const double* radii_sq, int E, int32_t* counts,
+              uint64_t* borderline, void* ws, size_t ws_bytes);
+int labels(hipStream_t s, int64_t n, int E, int e, int min_samples, const int32_t* counts, void* ws, size_t ws_bytes,
+           int32_t* labels_out, uint8_t* core_out, int32_t* n_clusters);
+}  // namespace dbscan
+
 }  // namespace hlmc

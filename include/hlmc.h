@@ -312,6 +312,28 @@ int64_t hlmc_cluster_scores_workspace(int k, int d);
 int hlmc_cluster_scores(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* out2,
                         void* ws, int64_t ws_bytes);
 
+/* ============================================================== DBSCAN
+ * sklearn.cluster.DBSCAN(eps, min_samples=5).fit_predict(latent_matrix) at src/Convolutional_VAE.py:353-354,382
+ * (float32 input, brute-force neighbourhoods), labels and core samples bit-identical to sklearn 1.7.
+ *
+ * hlmc_dbscan_neighbors: one pass over the fp64 (MFMA) distance tiles for E <= 32 squared radii.  i and j are
+ * neighbours for radius e iff max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) <= radii_sq[e], all in float64 on the float32
+ * rows.  radii_sq is a HOST array; for sklearn's float32 path pass (double)((float)eps * (float)eps).  Writes the
+ * bit-packed adjacency [E][n][ceil(n/64)] into the workspace, counts [E][n] int32 (neighbours of each row, self
+ * included) and borderline [E] uint64: pairs i < j with |d^2 - r| <= 4 (d + 4) 2^-53 (|x_i|^2 + |x_j|^2), the only
+ * ones another summation order could decide differently.  X [n][d] f32, 1 <= n <= 262144, d >= 1.
+ *
+ * hlmc_dbscan_labels: labels of radius e from the adjacency a preceding hlmc_dbscan_neighbors call (same n, E,
+ * workspace) left behind.  core [n] uint8 = (counts >= min_samples); clusters are the connected components of
+ * the core-core graph numbered by their smallest core index; a border point takes the smallest cluster number
+ * among its core neighbours; noise is -1.  n_clusters (nullable): device int32 scalar.  No host
+ * synchronisation, integer atomics only, deterministic. */
+int64_t hlmc_dbscan_workspace(int64_t n, int E);   /* bytes; 0 when n or E is out of range */
+int hlmc_dbscan_neighbors(void* stream, const float* X, int64_t n, int d, const double* radii_sq, int E, int32_t* counts,
+                          uint64_t* borderline, void* ws, int64_t ws_bytes);
+int hlmc_dbscan_labels(void* stream, int64_t n, int E, int e, int min_samples, const int32_t* counts, void* ws,
+                       int64_t ws_bytes, int32_t* labels, uint8_t* core, int32_t* n_clusters);
+
 
 /* ============================================================== op-level entry points
  * The kernels hlmc_net_* is built from, on NHWC activations (dtype HLMC_F32 / HLMC_BF16 for x, y, packed
