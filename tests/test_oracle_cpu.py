@@ -254,3 +254,52 @@ def test_oracle_training_chain_reproduces_fixture_latents(name):
     err = float(np.abs(mu.numpy() - fx).max())
     # bit-exact where the fixtures were generated (this container's CPU); Adam-amplified rounding elsewhere
     assert err == 0.0 or float(np.linalg.norm(mu.numpy() - fx) / np.linalg.norm(fx)) < 5e-2, err
+
+
+def test_adam_restatement_matches_torch_float64():
+    """oracle/optim_oracle.adam_step (the float64 yardstick of the GPU Adam tests) against torch.optim.Adam
+    (foreach=False) on float64 CPU tensors: 5 steps with weight decay and a large eps, every element within 1e-14
+    relative -- the parameters and exp_avg_sq relative to their own magnitude, exp_avg relative to |m| + |g + wd p|
+    of the step (it is a difference of those two terms: where they cancel, two correct float64 evaluations in a
+    different operation order, torch's lerp and the formula's, differ by more than 1e-14 of the small result)."""
+    from oracle import optim_oracle as OO
+    hp = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-3, weight_decay=1e-2)
+    g = torch.Generator().manual_seed(5)
+    ps = [torch.randn(s, dtype=torch.float64, generator=g).requires_grad_() for s in ((7, 13), (129,), (1,))]
+    opt = torch.optim.Adam(ps, foreach=False, **hp)
+    mine = [(p.detach().numpy().copy(), np.zeros(p.shape), np.zeros(p.shape)) for p in ps]
+    for step in range(1, 6):
+        for i, p in enumerate(ps):
+            p.grad = torch.randn(p.shape, dtype=torch.float64, generator=g) * 10.0 ** (i - 1)
+        opt.step()
+        scale_m = [np.abs(m) + np.abs(p.grad.numpy() + hp["weight_decay"] * q) for p, (q, m, v) in zip(ps, mine)]
+        mine = [OO.adam_step(q, p.grad.numpy(), m, v, hp["lr"], *hp["betas"], hp["eps"], hp["weight_decay"], step)
+                for p, (q, m, v) in zip(ps, mine)]
+        for p, (q, m, v), sm in zip(ps, mine, scale_m):
+            st = opt.state[p]
+            assert int(st["step"]) == step
+            for got, want, scale in ((q, p.detach(), None), (m, st["exp_avg"], sm), (v, st["exp_avg_sq"], None)):
+                want = want.numpy()
+                assert np.all(np.abs(got - want) <= 1e-14 * (np.abs(want) if scale is None else scale)), step
+
+
+def test_loss_restatement_matches_torch_float64_autograd():
+    """oracle/optim_oracle.loss_sums_and_grads against torch float64 autograd of the same three sums."""
+    from oracle import optim_oracle as OO
+    g = torch.Generator().manual_seed(6)
+    ra, a = torch.randn(301, dtype=torch.float64, generator=g), torch.randn(301, dtype=torch.float64, generator=g)
+    rt, t = torch.randn(17, dtype=torch.float64, generator=g), torch.randn(17, dtype=torch.float64, generator=g)
+    mu = 3 * torch.randn(33, dtype=torch.float64, generator=g)
+    lv = torch.rand(33, dtype=torch.float64, generator=g) * 18 - 12
+    coef = (2.0, 700.0, 4.0)
+    for x in (ra, rt, mu, lv):
+        x.requires_grad_()
+    s = (((ra - a) ** 2).sum(), ((rt - t) ** 2).sum(), (1 + lv - mu ** 2 - lv.exp()).sum())
+    (0.5 * coef[0] * s[0] + 0.5 * coef[1] * s[1] - 0.5 * coef[2] * s[2]).backward()
+    sums, dra, drt, dmu, dlv = OO.loss_sums_and_grads(*(x.detach().numpy() for x in (ra, a, rt, t, mu, lv)), coef)
+    np.testing.assert_allclose(sums, [float(x.detach()) for x in s], rtol=1e-13)
+    for got, x in ((dra, ra), (drt, rt), (dmu, mu), (dlv, lv)):
+        np.testing.assert_allclose(got, x.grad.numpy(), rtol=1e-13, atol=1e-13 * float(x.grad.abs().max()))
+    sums0, _, drt0, _, _ = OO.loss_sums_and_grads(ra.detach().numpy(), a.numpy(), None, None, mu.detach().numpy(),
+                                                  lv.detach().numpy(), coef)
+    assert sums0[1] == 0.0 and drt0 is None and sums0[0] == sums[0] and sums0[2] == sums[2]
