@@ -154,6 +154,28 @@ struct FastDiv {
     __device__ __forceinline__ uint32_t div(uint32_t n) const { return (__umulhi(n, mul) + n) >> sh; }
 };
 
+// The conv stacks' low-res map [B, hw pixels, C] in its two orders: NHWC (pixel row m = b * hw + p, channel c at
+// m * C + c) and the NCHW-flat rows of the dense layers next to it (row b of stride ld, column f = c * hw + p).
+// The kernels that produce such a map store it in the consumer's order through this (no relayout pass); hw is any
+// positive count (4 at 128 x 128 mels, 6 at 192 x 128).
+struct FlatIdx {
+    int hw = 0, C = 0, ld = 0;
+    FastDiv dhw;
+    FlatIdx() = default;
+    FlatIdx(int hw_, int C_, int ld_) : hw(hw_), C(C_), ld(ld_), dhw((uint32_t)hw_) {}
+    // flat offset of channel 0 of NHWC row m; channel c is c * hw further
+    __device__ __forceinline__ int64_t flat_row(int m) const {
+        const int b = (int)dhw.div((uint32_t)m);
+        return (int64_t)b * ld + (m - b * hw);
+    }
+    __device__ __forceinline__ int64_t flat(int m, int c) const { return flat_row(m) + (int64_t)c * hw; }
+    // NHWC offset of column f (< C * hw) of flat row b
+    __device__ __forceinline__ int64_t nhwc(int b, int f) const {
+        const int c = (int)dhw.div((uint32_t)f);
+        return ((int64_t)b * hw + (f - c * hw)) * C + c;
+    }
+};
+
 
 // ------------------------------------------------------------------ exact column-sum accumulators
 // Per-column sums that many blocks of one launch contribute to (BatchNorm batch statistics, backward moments, bias

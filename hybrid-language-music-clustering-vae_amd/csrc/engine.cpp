@@ -43,16 +43,31 @@ class NetT : public NetBase {
         p.d1 = (int)sh[1];
         p.taps = taps;
     }
+    // Two linear layers of one shape that read the same input (the latent heads) share their forward pack, so their
+    // forward is one GEMM: P0 is one [2 d0][ld0] matrix (w0's rows, then w1's), addressed by P0(w0).  Each keeps its
+    // own transposed pack P1: their data gradients stay two unsplit GEMMs (see heads_bwd).
+    std::vector<std::pair<int, int>> pack_pairs;
+    void pair_packs(int w0, int w1) { pack_pairs.emplace_back(w0, w1); }
     void finalize_state() {
         packs.resize(params.size());
         Arena A;
+        for (const auto& pr : pack_pairs) {
+            Pack &p = packs[pr.first], &q = packs[pr.second];
+            p.ld0 = q.ld0 = pad8(p.d1);
+            p.ld1 = q.ld1 = pad8(p.d0);
+            p.off0 = A.take((size_t)2 * p.d0 * p.ld0 * sizeof(T));
+            q.off0 = p.off0 + (size_t)p.d0 * p.ld0 * sizeof(T);
+            p.off1 = A.take((size_t)p.d1 * p.ld1 * sizeof(T));
+            q.off1 = A.take((size_t)q.d1 * q.ld1 * sizeof(T));
+        }
         for (auto& p : packs) {
             if (!p.taps) continue;
+            ++njobs;
+            if (p.off0 != SIZE_MAX) continue;  // half of a pair
             p.ld0 = p.taps == 1 ? pad8(p.d1) : p.d1;
             p.ld1 = p.taps == 1 ? pad8(p.d0) : p.d0;
             p.off0 = A.take((size_t)p.d0 * p.taps * p.ld0 * sizeof(T));
             p.off1 = A.take((size_t)p.d1 * p.taps * p.ld1 * sizeof(T));
-            ++njobs;
         }
         jobs_off = A.take(sizeof(ops::AdamJob) * std::max<size_t>(1, njobs));
         ajobs_off = A.take(sizeof(ops::AdamJob) * std::max<size_t>(1, params.size()));
@@ -335,6 +350,30 @@ class NetT : public NetBase {
         const ops::CopySeg cs[2] = {{a.mu, mu, nl}, {a.logvar, lv, nl}};
         return ops::copy_segments(s, cs, 2);
     }
+    // The latent heads (paired packs, pair_packs) as one GEMM over x to fp32 partials and one reduce launch that
+    // adds the biases, writes mu / lv and the caller's latent outputs and -- unless a.encode_only -- reparameterises
+    // like reparam() above: z (row stride ldz) and the kept eps, from a.eps or the net's Philox stream.
+    int heads_fwd(hipStream_t s, const ForwardArgs& a, const T* x, int ldx, int B, int L, int mu_w, int mu_b, int lv_b,
+                  float* mu, float* lv, float* eps_keep, T* z, int ldz) {
+        const int K = (int)params[mu_w].shape[1];
+        int S = 0;
+        HLMC_TRY(ops::linear_partials<T>(s, x, ldx, B, K, P0(mu_w), ld0(mu_w), 2 * L, scratch, &S));
+        if (a.encode_only)
+            return ops::heads_reparam<T>(s, scratch.p, S, B, L, P[mu_b], P[lv_b], mu, lv, a.mu, a.logvar, nullptr, 0, 0,
+                                         nullptr, nullptr, 0);
+        uint64_t off = 0;
+        if (!a.eps) {
+            off = this->rng_offset;
+            this->rng_offset += ((uint64_t)B * L + 3) & ~uint64_t(3);
+        }
+        return ops::heads_reparam<T>(s, scratch.p, S, B, L, P[mu_b], P[lv_b], mu, lv, a.mu, a.logvar, a.eps,
+                                     this->rng_seed, off, eps_keep, z, ldz);
+    }
+    void heads_need(int B, int L, int K) {
+        need(ops::linear_partials_ws<T>(B, K, 2 * L));
+        need(ops::linear_ws<T>(B, L, K));
+        need(ops::linear_wgrad_ws<T>(B, 2 * L, K));
+    }
 
     // ---------------------------------------------------------------- layer helpers
     // y = act(x W^T + b)
@@ -354,23 +393,71 @@ class NetT : public NetBase {
     // the fork's event first, then dx (+=) on s — the critical path, with the ReLU backward of the layer below
     // (relu_ref: its post-ReLU output) in the epilogue — then dW and db as ONE weight-gradient GEMM (a ones
     // column on x gives db) on the weight-gradient stream: 2-3 launches where there were 6-7.
+    // no (nullable): dx's first columns are written in NHWC order (ops::NhwcOut: the conv encoder's gradient)
     int lin_bwd(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int B, int w, int b, T* dx, int lddx,
-                int acc = 0, const T* relu_ref = nullptr) {
+                int acc = 0, const T* relu_ref = nullptr, const ops::NhwcOut* no = nullptr) {
         const int N = (int)params[w].shape[0], K = (int)params[w].shape[1];
         float* gw = G[w];
         float* gb = b >= 0 ? G[b] : nullptr;
-        SideFn wg = [=](hipStream_t q, Ws sc) { return ops::linear_wgrad<T>(q, dy, lddy, x, ldx, B, N, K, gw, gb, sc); };
+        const T* p1 = P1(w);
+        const int ldw = ld1(w);
+        return dense_bwd(
+            s, [=](hipStream_t q, Ws sc) { return ops::linear_wgrad<T>(q, dy, lddy, x, ldx, B, N, K, gw, gb, sc); },
+            [=]() {
+                if (!dx) return (int)HLMC_OK;
+                return ops::linear<T, T>(s, dy, lddy, B, N, p1, ldw, nullptr, K, dx, lddx, 0, acc, scratch, relu_ref, no);
+            });
+    }
+    // wg: the layer's weight-gradient launch (weight-gradient stream), dxf: its data-gradient launches (on s)
+    template <class DxFn>
+    int dense_bwd(hipStream_t s, SideFn wg, DxFn dxf) {
         if (!dense_side_on()) {
-            if (dx)
-                HLMC_TRY(ops::linear<T, T>(s, dy, lddy, B, N, P1(w), ld1(w), nullptr, K, dx, lddx, 0, acc, scratch, relu_ref));
+            HLMC_TRY(dxf());
             return wg(s, scratch);
         }
         side_q.push_back(std::move(wg));
         const bool go = (int)side_q.size() >= dense_batch();
         if (go) HLMC_TRY(fork(s));
-        if (dx)
-            HLMC_TRY(ops::linear<T, T>(s, dy, lddy, B, N, P1(w), ld1(w), nullptr, K, dx, lddx, 0, acc, scratch, relu_ref));
+        HLMC_TRY(dxf());
         return go ? issue_side() : HLMC_OK;
+    }
+    // The latent heads' backward from gml = [gmu | glv] ([B][ldg], 2L columns): both layers' weight and bias gradients
+    // as one launch.  The data gradient stays two GEMMs over the column halves, the second accumulating (relu_ref / no
+    // as lin_bwd): with K = L each runs unsplit, so they are two launches, as many as one merged GEMM (K = 2L takes two
+    // splits and a reduce; kept unsplit it measured slower), and the result keeps the bits it had.
+    int heads_bwd(hipStream_t s, const T* gml, int ldg, const T* x, int ldx, int B, int L, int mu_w, int mu_b, int lv_w,
+                  int lv_b, T* dx, int lddx, const T* relu_ref, const ops::NhwcOut* no) {
+        const int K = (int)params[mu_w].shape[1];
+        float *gw1 = G[mu_w], *gb1 = G[mu_b], *gw2 = G[lv_w], *gb2 = G[lv_b];
+        const T *p1m = P1(mu_w), *p1l = P1(lv_w);
+        const int ldm = ld1(mu_w), ldl = ld1(lv_w);
+        return dense_bwd(
+            s,
+            [=](hipStream_t q, Ws sc) {
+                return ops::linear_wgrad_pair<T>(q, gml, ldg, x, ldx, B, L, K, gw1, gb1, gw2, gb2, sc);
+            },
+            [=]() {
+                HLMC_TRY(ops::linear<T, T>(s, gml, ldg, B, L, p1m, ldm, nullptr, K, dx, lddx, 0, 0, scratch, nullptr, no));
+                return ops::linear<T, T>(s, gml + L, ldg, B, L, p1l, ldl, nullptr, K, dx, lddx, 0, 1, scratch, relu_ref, no);
+            });
+    }
+    // The backward of the layer that reads z (weight w [N][>= L]; x = z's buffer) with the reparameterisation
+    // backward in its data gradient's reduce launch: dz (the first L columns only) is not stored, and
+    // gml = [gmu | glv] (the heads' operand, heads_bwd) is written directly
+    int z_bwd(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int B, int L, int w, int b, const float* lv,
+              const float* eps, const float* d_mu, const float* d_lv, T* gml, int ldg) {
+        const int N = (int)params[w].shape[0], K = (int)params[w].shape[1];
+        float* gw = G[w];
+        float* gb = b >= 0 ? G[b] : nullptr;
+        const T* p1 = P1(w);
+        const int ldw = ld1(w);
+        return dense_bwd(
+            s, [=](hipStream_t q, Ws sc) { return ops::linear_wgrad<T>(q, dy, lddy, x, ldx, B, N, K, gw, gb, sc); },
+            [=]() {
+                int S = 0;
+                HLMC_TRY(ops::linear_partials<T>(s, dy, lddy, B, N, p1, ldw, L, scratch, &S));
+                return ops::reparam_bwd_reduce<T>(s, scratch.p, S, B, L, lv, eps, d_mu, d_lv, gml, gml + L, ldg);
+            });
     }
 
     struct BnBufs {
@@ -400,15 +487,17 @@ class NetT : public NetBase {
     XAcc acc_mom(const BnBufs& b) const { return acc_at(xb_base + b.xb, b.C, 2 * b.C); }
     XAcc acc_bias(const BnBufs& b) const { return acc_at(xb_base + b.xbias, b.C, b.C); }
     // st: statistics already delivered by the producing kernel (st->done), else a moments pass first
+    // fo / hw (nullable): a is written NCHW-flat (ops::FlatOut; R = B * hw pixels)
     int bn_fwd(hipStream_t s, bool train, const T* y, int64_t R, int C, int bn, const BnBufs& bb, int g, int beta, int act,
-               const uint8_t* mask, float mscale, T* a, int lda, const ops::ColStats* st = nullptr) {
+               const uint8_t* mask, float mscale, T* a, int lda, const ops::ColStats* st = nullptr,
+               const ops::FlatOut* fo = nullptr, int hw = 0) {
         float* mean = AF(bb.mean);
         float* inv = AF(bb.inv);
         if (train)  // statistics finalized inside the activation kernel
             return ops::bn_act_train<T>(s, y, R, C, acc_fwd(bb), st && st->done, mean, inv, RM[bn], RV[bn], NBT[bn],
-                                        kBnMomentum, kBnEps, P[g], P[beta], act, mask, mscale, a, lda);
+                                        kBnMomentum, kBnEps, P[g], P[beta], act, mask, mscale, a, lda, fo, hw);
         HLMC_TRY(ops::bn_eval_stats(s, RM[bn], RV[bn], C, kBnEps, mean, inv));
-        return ops::bn_act<T>(s, y, R, C, mean, inv, P[g], P[beta], act, mask, mscale, a, lda);
+        return ops::bn_act<T>(s, y, R, C, mean, inv, P[g], P[beta], act, mask, mscale, a, lda, fo, hw);
     }
     // fused: moments delivered by the kernel that wrote da (nullable); bias_side: the conv bias column sums are
     // reduced into the gradient on the weight-gradient stream (else here)
@@ -458,7 +547,7 @@ class NetT : public NetBase {
     struct Enc {
         int w[6], b[6], g[6], beta[6], bn[6];
         int H = 0, W = 0;
-        size_t y[6], a[6], dy[6];  // dy: grad wrt the conv output (read by the forked wgrad)
+        size_t y[6], a[6], dy[6];  // dy: grad wrt the conv output (read by the forked wgrad); a[5]: see enc_fwd
         // the caller's input of the last full forward: the first conv's weight gradient reads it in backward (the
         // ABI contract keeps in0 alive and unchanged until then: hlmc.h hlmc_net_forward)
         const float* audio = nullptr;
@@ -491,7 +580,7 @@ class NetT : public NetBase {
             w /= 2;
             const size_t n = (size_t)B * h * w * co;
             enc.y[l] = A.take(n * sizeof(T));
-            enc.a[l] = A.take(n * sizeof(T));
+            enc.a[l] = l < 5 ? A.take(n * sizeof(T)) : 0;
             enc.dy[l] = A.take(n * sizeof(T));
             enc.bb[l] = bn_plan(A, co);
         }
@@ -503,7 +592,9 @@ class NetT : public NetBase {
         return ops::BnInput{acc_fwd(bb), R, AF(bb.mean), AF(bb.inv), RM[bn], RV[bn], NBT[bn], kBnMomentum, kBnEps,
                             P[g], P[beta], ws + a_off};
     }
-    int enc_fwd(hipStream_t s, bool train, const float* audio_in, int B) {
+    // The last layer's activation is written NCHW-flat straight into the dense layer's input rows flat ([B][ldflat]):
+    // nothing reads it in NHWC order (the backward of a layer reads its pre-BN map y and the activation below it).
+    int enc_fwd(hipStream_t s, bool train, const float* audio_in, int B, T* flat, int ldflat) {
         int h = enc.H, w = enc.W;
         HLMC_CHECK_ARG(audio_in, "audio input required");
         const float* audio = audio_in;
@@ -527,6 +618,10 @@ class NetT : public NetBase {
             if (fused_prev) {
                 if (!st.done) HLMC_TRY(ops::bn_moments<T>(s, y, R, co, acc_fwd(enc.bb[l])));  // e.g. a split-K producer
                 xin = bn_input(enc.bb[l], enc.bn[l], enc.g[l], enc.beta[l], R, enc.a[l]);
+            } else if (l == 5) {
+                const ops::FlatOut fo{ldflat, nullptr};
+                HLMC_TRY(bn_fwd(s, train, y, R, co, enc.bn[l], enc.bb[l], enc.g[l], enc.beta[l], 0, nullptr, 1.f, flat, 0,
+                                &st, &fo, h * w));
             } else
                 HLMC_TRY(bn_fwd(s, train, y, R, co, enc.bn[l], enc.bb[l], enc.g[l], enc.beta[l], 0, nullptr, 1.f,
                                 AT(enc.a[l]), co, &st));
@@ -650,8 +745,9 @@ class NetT : public NetBase {
         }
         return HLMC_OK;
     }
-    // gA: data-gradient chain buffer; returns the grad wrt u in *out (= gA)
-    int dec_bwd(hipStream_t s, const T* u, int B, const float* d_recon, T* gA, T** out) {
+    // gA: data-gradient chain buffer.  The grad wrt u is written NCHW-flat to gflat ([B][ldflat]: the operand of the
+    // dense layer below), zeroed where relu_ref (nullable: u, when it is a ReLU's output) is not positive
+    int dec_bwd(hipStream_t s, const T* u, int B, const float* d_recon, T* gA, T* gflat, int ldflat, const T* relu_ref) {
         int hs[7], ws_[7];
         hs[0] = dec.h0;
         ws_[0] = dec.w0;
@@ -687,10 +783,11 @@ class NetT : public NetBase {
             HLMC_TRY(side_bias(s, [=](hipStream_t q, Ws sc) {
                 return ops::wgrad_s2<T>(q, xin, B, hl, wl, ci, dy, co, gw, sc, pb.acc, pb.gb);
             }));
-            HLMC_TRY(ops::conv_s2<T>(s, dy, B, 2 * hl, 2 * wl, co, P0(dec.w[l]), nullptr, ci, gA, scratch));
+            const ops::FlatOut fo{ldflat, relu_ref};
+            HLMC_TRY(ops::conv_s2<T>(s, dy, B, 2 * hl, 2 * wl, co, P0(dec.w[l]), nullptr, ci, l == 0 ? gflat : gA, scratch,
+                                     nullptr, nullptr, l == 0 ? &fo : nullptr));
             fuse = ops::BnBwdFuse{};  // the stride-2 conv data gradients carry no moments: a separate pass
         }
-        *out = gA;
         return HLMC_OK;
     }
 };
@@ -714,10 +811,10 @@ class HybridNet : public NetT<T> {
     int td_w[2], td_b[2], td_g, td_beta, td_bn;
     int FU = 1024, SP = 1024;  // fusion / split widths
     // workspace
-    size_t flat_, fuse_, tin_, te_y[2], te_a0, h_, mu_, lv_, eps_, z_, d1_, s_, ah_, u_, td_y, td_a, rt_;
+    size_t flat_, fuse_, tin_, te_y[2], te_a0, h_, mu_, lv_, eps_, z_, d1_, s_, u_, td_y, td_a, rt_;
     BnBufs te_bb[2], td_bb;
-    size_t gA_, gflat_, gfuse_, gh_, gz_, gd1_, gs_, gah_, gte_, gte1_, gte2_, gtd_, gtd2_, gmuT_, glvT_, grt_;
-    int ldF = 0, ldT = 0, ldFU = 0, ldSP = 0;
+    size_t gA_, gfuse_, gh_, gd1_, gs_, gah_, gte_, gte1_, gte2_, gtd_, gtd2_, gml_, grt_;
+    int ldF = 0, ldT = 0, ldFU = 0, ldSP = 0, ldG = 0;
 
     HybridNet(int latent, int text_dim, int h, int w) : L(latent), TD(text_dim), H(h), W(w) {
         text = text_dim > 0;
@@ -756,6 +853,7 @@ class HybridNet : public NetT<T> {
         adf_w = this->add_param("audio_decoder_fc.weight", {F, 1024});
         adf_b = this->add_param("audio_decoder_fc.bias", {F});
         for (int w : {fus_w, mu_w, lv_w, di_w, ds_w, adf_w}) this->register_pack(w, 1);
+        this->pair_packs(mu_w, lv_w);
         this->dec_register("audio_decoder", 1);
         if (text) {
             td_w[0] = this->add_param("text_decoder.0.weight", {256, 128});
@@ -779,6 +877,7 @@ class HybridNet : public NetT<T> {
         ldT = pad8(TD);
         ldFU = pad8(FU);
         ldSP = pad8(SP);
+        ldG = pad8(2 * L);
         this->enc_plan(A, B);
         this->dec_plan(A, B);
         const size_t t = sizeof(T);
@@ -791,7 +890,6 @@ class HybridNet : public NetT<T> {
         z_ = A.take(B * L * t);
         d1_ = A.take(B * 512 * t);
         s_ = A.take(B * ldSP * t);
-        ah_ = A.take(B * ldF * t);
         u_ = A.take(B * ldF * t);
         if (text) {
             tin_ = A.take(B * ldT * t);
@@ -816,23 +914,20 @@ class HybridNet : public NetT<T> {
         }
         const size_t gmax = std::max(this->enc_max_elems(B), this->dec_max_elems(B));
         gA_ = A.take(gmax * t);
-        gflat_ = A.take(B * ldF * t);
         gfuse_ = A.take(B * ldFU * t);
         gh_ = A.take(B * 512 * t);
-        gz_ = A.take(B * L * t);
         gd1_ = A.take(B * 512 * t);
         gs_ = A.take(B * ldSP * t);
         gah_ = A.take(B * ldF * t);
-        gmuT_ = A.take(B * L * t);
-        glvT_ = A.take(B * L * t);
-        for (int w : {afc_w, fus_w, mu_w, lv_w, di_w, ds_w, adf_w}) this->lin_need((int)B, w);
+        gml_ = A.take(B * ldG * t);
+        for (int w : {afc_w, fus_w, di_w, ds_w, adf_w}) this->lin_need((int)B, w);
+        this->heads_need((int)B, L, 512);
+        this->need(ops::linear_partials_ws<T>((int)B, 512, L));
     }
 
     int encode(hipStream_t s, const ForwardArgs& a, int B) {
         const bool tr = a.train != 0;
-        HLMC_TRY(this->enc_fwd(s, tr, a.in0, B));
-        const int hh = H / 64, ww = W / 64;
-        HLMC_TRY(ops::nhwc_to_flat<T>(s, AT(this->enc.a[5]), B, hh, ww, 512, AT(flat_), ldF));
+        HLMC_TRY(this->enc_fwd(s, tr, a.in0, B, AT(flat_), ldF));
         HLMC_TRY(this->template lin_fwd<T>(s, AT(flat_), ldF, B, afc_w, afc_b, AT(fuse_), ldFU, 0));
         if (text) {
             HLMC_CHECK_ARG(a.in1, "text input required");
@@ -845,9 +940,8 @@ class HybridNet : public NetT<T> {
                                   AT(fuse_) + 1024, ldFU));
         }
         HLMC_TRY(this->template lin_fwd<T>(s, AT(fuse_), ldFU, B, fus_w, fus_b, AT(h_), 512, 1));
-        HLMC_TRY(this->template lin_fwd<float>(s, AT(h_), 512, B, mu_w, mu_b, AF(mu_), L, 0));
-        HLMC_TRY(this->template lin_fwd<float>(s, AT(h_), 512, B, lv_w, lv_b, AF(lv_), L, 0));
-        return HLMC_OK;
+        // mu, logvar, the caller's copies, the kept eps and z: one GEMM and its reduce launch
+        return this->heads_fwd(s, a, AT(h_), 512, B, L, mu_w, mu_b, lv_b, AF(mu_), AF(lv_), AF(eps_), AT(z_), L);
     }
 
     int forward(hipStream_t s, const ForwardArgs& a) override {
@@ -863,16 +957,16 @@ class HybridNet : public NetT<T> {
             HLMC_CHECK_ARG(a.in0 && a.recon, "z and recon required");
             HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, L, AT(z_), L, B, L));
         } else {
+            HLMC_CHECK_ARG(a.encode_only || a.recon, "recon required");
             HLMC_TRY(encode(s, a, B));
-            if (a.encode_only) return this->latent_out(s, a, AF(mu_), AF(lv_), (int64_t)B * L);
-            HLMC_CHECK_ARG(a.recon, "recon required");
-            // z, the kept eps and the caller's mu / logvar outputs in one launch
-            HLMC_TRY(this->reparam(s, a.eps, AF(mu_), AF(lv_), AF(eps_), B, L, AT(z_), L, a.mu, a.logvar));
+            if (a.encode_only) return HLMC_OK;
         }
         HLMC_TRY(this->template lin_fwd<T>(s, AT(z_), L, B, di_w, di_b, AT(d1_), 512, 1));
         HLMC_TRY(this->template lin_fwd<T>(s, AT(d1_), 512, B, ds_w, ds_b, AT(s_), ldSP, 1));
-        HLMC_TRY(this->template lin_fwd<T>(s, AT(s_), ldSP, B, adf_w, adf_b, AT(ah_), ldF, 1));
-        HLMC_TRY(ops::flat_to_nhwc<T>(s, AT(ah_), ldF, B, H / 64, W / 64, 512, AT(u_)));
+        // audio_decoder_fc writes the decoder's NHWC input directly (bias / ReLU by the flat column)
+        const ops::NhwcOut no{AT(u_), F, (H / 64) * (W / 64), 512};
+        HLMC_TRY(ops::linear<T, T>(s, AT(s_), ldSP, B, 1024, this->P0(adf_w), this->ld0(adf_w), P[adf_b], F, AT(u_), ldF, 1,
+                                   0, this->scratch, nullptr, &no));
         HLMC_TRY(this->dec_fwd(s, a.train != 0, AT(u_), B, a.recon));
         if (text) {
             HLMC_CHECK_ARG(a.recon_text, "recon_text required");
@@ -904,18 +998,16 @@ class HybridNet : public NetT<T> {
                                    AT(s_) + 1024));
         }
         // ---- audio decoder
-        T* gu = nullptr;
-        HLMC_TRY(this->dec_bwd(s, AT(u_), B, a.d_recon, gA, &gu));
+        // (each ReLU backward rides in the epilogue of the GEMM that writes the gradient: here audio_decoder_fc's, in
+        // the store of the first decoder layer's data gradient, which also writes the flat order gah_ is read in)
+        HLMC_TRY(this->dec_bwd(s, AT(u_), B, a.d_recon, gA, AT(gah_), ldF, AT(u_)));
         HLMC_TRY(this->mark(s, 0));
-        // (each ReLU backward rides in the epilogue of the GEMM / relayout that writes the gradient)
-        HLMC_TRY(ops::nhwc_to_flat<T>(s, gu, B, H / 64, W / 64, 512, AT(gah_), ldF, AT(ah_)));
         HLMC_TRY(this->lin_bwd(s, AT(gah_), ldF, AT(s_), ldSP, B, adf_w, adf_b, AT(gs_), ldSP, 0, AT(s_)));
         HLMC_TRY(this->lin_bwd(s, AT(gs_), ldSP, AT(d1_), 512, B, ds_w, ds_b, AT(gd1_), 512, 0, AT(d1_)));
-        HLMC_TRY(this->lin_bwd(s, AT(gd1_), 512, AT(z_), L, B, di_w, di_b, AT(gz_), L));
-        // ---- reparameterisation + heads: one pass to the heads' T gradients (the caller's d_mu / d_logvar added)
-        HLMC_TRY(ops::reparam_bwd<T>(s, AT(gz_), L, AF(lv_), AF(eps_), a.d_mu, a.d_logvar, B, L, AT(gmuT_), AT(glvT_)));
-        HLMC_TRY(this->lin_bwd(s, AT(gmuT_), L, AT(h_), 512, B, mu_w, mu_b, AT(gh_), 512, 0));
-        HLMC_TRY(this->lin_bwd(s, AT(glvT_), L, AT(h_), 512, B, lv_w, lv_b, AT(gh_), 512, 1, AT(h_)));
+        // ---- reparameterisation (in decoder_input's data-gradient reduce; the caller's d_mu / d_logvar added) + heads
+        HLMC_TRY(this->z_bwd(s, AT(gd1_), 512, AT(z_), L, B, L, di_w, di_b, AF(lv_), AF(eps_), a.d_mu, a.d_logvar,
+                             AT(gml_), ldG));
+        HLMC_TRY(this->heads_bwd(s, AT(gml_), ldG, AT(h_), 512, B, L, mu_w, mu_b, lv_w, lv_b, AT(gh_), 512, AT(h_), nullptr));
         HLMC_TRY(this->lin_bwd(s, AT(gh_), 512, AT(fuse_), ldFU, B, fus_w, fus_b, AT(gfuse_), ldFU));
         // ---- text encoder
         if (text) {
@@ -927,9 +1019,10 @@ class HybridNet : public NetT<T> {
             HLMC_TRY(this->lin_bwd(s, AT(gte2_), 256, AT(tin_), ldT, B, te_w[0], -1, nullptr, 0));
         }
         // ---- audio encoder
-        HLMC_TRY(this->lin_bwd(s, AT(gfuse_), ldFU, AT(flat_), ldF, B, afc_w, afc_b, AT(gflat_), ldF));
+        // audio_fc's data gradient in the encoder's NHWC order
+        const ops::NhwcOut no{gA, F, (H / 64) * (W / 64), 512};
+        HLMC_TRY(this->lin_bwd(s, AT(gfuse_), ldFU, AT(flat_), ldF, B, afc_w, afc_b, gA, ldF, 0, nullptr, &no));
         HLMC_TRY(this->mark(s, 1));
-        HLMC_TRY(ops::flat_to_nhwc<T>(s, AT(gflat_), ldF, B, H / 64, W / 64, 512, gA));
         HLMC_TRY(this->enc_bwd(s, B, gA, 2));
         HLMC_TRY(this->finish_backward(s));
         return this->mark(s, 3);
@@ -954,7 +1047,8 @@ class CvaeNet : public NetT<T> {
     int ldF = 0, ldT = 0, ldX = 0, ldZ = 0, ldS = 0;
     size_t tin_, te_y, X_, mu_, lv_, eps_, Z_, S_, u_, td_y, td_a;
     BnBufs te_bb, td_bb;
-    size_t gA_, grt_, gtd_, gt2_, gt3_, gS_, gZ_, gX_, gmuT_, glvT_;
+    size_t gA_, grt_, gtd_, gt2_, gt3_, gS_, gX_, gml_;
+    int ldG = 0;
 
     CvaeNet(int latent, int text_dim, int ncls, int h, int w) : L(latent), TD(text_dim), C(ncls), H(h), W(w) {
         F = 512 * (H / 64) * (W / 64);
@@ -983,6 +1077,7 @@ class CvaeNet : public NetT<T> {
         td_w[1] = this->add_param("text_decoder.3.weight", {TD, 512});
         td_b[1] = this->add_param("text_decoder.3.bias", {TD});
         for (int w_ : {te_w, mu_w, lv_w, dfc_w, td_w[0], td_w[1]}) this->register_pack(w_, 1);
+        this->pair_packs(mu_w, lv_w);
         this->dec_register("audio_decoder", 0);
         this->finalize_state();
         // backward finishes: text + audio decoder | text_encoder .. decoder_fc | encoder layers 3-5 | layers 0-2
@@ -997,6 +1092,7 @@ class CvaeNet : public NetT<T> {
         ldX = pad8(F + 256 + C);
         ldZ = pad8(L + C);
         ldS = pad8(F + 256);
+        ldG = pad8(2 * L);
         this->enc_plan(A, B);
         this->dec_plan(A, B);
         tin_ = A.take(B * ldT * t);
@@ -1019,25 +1115,23 @@ class CvaeNet : public NetT<T> {
         gt2_ = A.take(B * 512 * t);
         gt3_ = A.take(B * 256 * t);
         gS_ = A.take(B * ldS * t);
-        gZ_ = A.take(B * ldZ * t);
         gX_ = A.take(B * ldX * t);
-        gmuT_ = A.take(B * L * t);
-        glvT_ = A.take(B * L * t);
-        for (int w_ : {te_w, mu_w, lv_w, dfc_w, td_w[0], td_w[1]}) this->lin_need((int)B, w_);
+        gml_ = A.take(B * ldG * t);
+        for (int w_ : {te_w, dfc_w, td_w[0], td_w[1]}) this->lin_need((int)B, w_);
+        this->heads_need((int)B, L, F + 256 + C);
+        this->need(ops::linear_partials_ws<T>((int)B, F + 256, L));
     }
 
     int encode(hipStream_t s, const ForwardArgs& a, int B) {
         const bool tr = a.train != 0;
         HLMC_CHECK_ARG(a.in1 && a.in2, "text and condition inputs required");
-        HLMC_TRY(this->enc_fwd(s, tr, a.in0, B));
-        HLMC_TRY(ops::nhwc_to_flat<T>(s, AT(this->enc.a[5]), B, H / 64, W / 64, 512, AT(X_), ldX));
+        HLMC_TRY(this->enc_fwd(s, tr, a.in0, B, AT(X_), ldX));
         HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in1, TD, AT(tin_), ldT, B, TD));
         HLMC_TRY(this->template lin_fwd<T>(s, AT(tin_), ldT, B, te_w, te_b, AT(te_y), 256, 0));
         HLMC_TRY(this->bn_fwd(s, tr, AT(te_y), B, 256, te_bn, te_bb, te_g, te_beta, 0, nullptr, 1.f, AT(X_) + F, ldX));
         HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in2, C, AT(X_) + F + 256, ldX, B, C));
-        HLMC_TRY(this->template lin_fwd<float>(s, AT(X_), ldX, B, mu_w, mu_b, AF(mu_), L, 0));
-        HLMC_TRY(this->template lin_fwd<float>(s, AT(X_), ldX, B, lv_w, lv_b, AF(lv_), L, 0));
-        return HLMC_OK;
+        // mu, logvar, the caller's copies, the kept eps and z: one GEMM and its reduce launch
+        return this->heads_fwd(s, a, AT(X_), ldX, B, L, mu_w, mu_b, lv_b, AF(mu_), AF(lv_), AF(eps_), AT(Z_), ldZ);
     }
 
     int forward(hipStream_t s, const ForwardArgs& a) override {
@@ -1053,15 +1147,15 @@ class CvaeNet : public NetT<T> {
             HLMC_CHECK_ARG(a.in0 && a.in2 && a.recon && a.recon_text, "z / condition / recon / recon_text required");
             HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, L, AT(Z_), ldZ, B, L));
         } else {
+            HLMC_CHECK_ARG(a.encode_only || (a.recon && a.recon_text), "recon / recon_text required");
             HLMC_TRY(encode(s, a, B));
-            if (a.encode_only) return this->latent_out(s, a, AF(mu_), AF(lv_), (int64_t)B * L);
-            HLMC_CHECK_ARG(a.recon && a.recon_text, "recon / recon_text required");
-            // z, the kept eps and the caller's mu / logvar outputs in one launch
-            HLMC_TRY(this->reparam(s, a.eps, AF(mu_), AF(lv_), AF(eps_), B, L, AT(Z_), ldZ, a.mu, a.logvar));
+            if (a.encode_only) return HLMC_OK;
         }
         HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in2, C, AT(Z_) + L, ldZ, B, C));
-        HLMC_TRY(this->template lin_fwd<T>(s, AT(Z_), ldZ, B, dfc_w, dfc_b, AT(S_), ldS, 0));
-        HLMC_TRY(ops::flat_to_nhwc<T>(s, AT(S_), ldS, B, H / 64, W / 64, 512, AT(u_)));
+        // decoder_fc writes its audio columns as the decoder's NHWC input, the text columns to S_
+        const ops::NhwcOut no{AT(u_), F, (H / 64) * (W / 64), 512};
+        HLMC_TRY(ops::linear<T, T>(s, AT(Z_), ldZ, B, L + C, this->P0(dfc_w), this->ld0(dfc_w), P[dfc_b], F + 256, AT(S_),
+                                   ldS, 0, 0, this->scratch, nullptr, &no));
         HLMC_TRY(this->dec_fwd(s, a.train != 0, AT(u_), B, a.recon));
         HLMC_TRY(this->template lin_fwd<T>(s, AT(S_) + F, ldS, B, td_w[0], td_b[0], AT(td_y), 512, 0));
         HLMC_TRY(this->bn_fwd(s, a.train != 0, AT(td_y), B, 512, td_bn, td_bb, td_g, td_beta, 0, nullptr, 1.f, AT(td_a), 512));
@@ -1085,22 +1179,20 @@ class CvaeNet : public NetT<T> {
         HLMC_TRY(this->bn_bwd(s, AT(gtd_), 512, AT(td_y), B, 512, td_bb, td_g, td_beta, 0, nullptr, 1.f, AT(gt2_), td_b[0]));
         HLMC_TRY(this->lin_bwd(s, AT(gt2_), 512, AT(S_) + F, ldS, B, td_w[0], -1, AT(gS_) + F, ldS));
         // audio decoder
-        T* gu = nullptr;
-        HLMC_TRY(this->dec_bwd(s, AT(u_), B, a.d_recon, gA, &gu));
+        // (the first layer's data gradient is written in decoder_fc's flat order; no activation in between)
+        HLMC_TRY(this->dec_bwd(s, AT(u_), B, a.d_recon, gA, AT(gS_), ldS, nullptr));
         HLMC_TRY(this->mark(s, 0));
-        HLMC_TRY(ops::nhwc_to_flat<T>(s, gu, B, H / 64, W / 64, 512, AT(gS_), ldS));
-        // decoder_fc (no activation)
-        HLMC_TRY(this->lin_bwd(s, AT(gS_), ldS, AT(Z_), ldZ, B, dfc_w, dfc_b, AT(gZ_), ldZ));
-        // reparameterisation
-        HLMC_TRY(ops::reparam_bwd<T>(s, AT(gZ_), ldZ, AF(lv_), AF(eps_), a.d_mu, a.d_logvar, B, L, AT(gmuT_), AT(glvT_)));
-        HLMC_TRY(this->lin_bwd(s, AT(gmuT_), L, AT(X_), ldX, B, mu_w, mu_b, AT(gX_), ldX, 0));
-        HLMC_TRY(this->lin_bwd(s, AT(glvT_), L, AT(X_), ldX, B, lv_w, lv_b, AT(gX_), ldX, 1));
+        // decoder_fc with the reparameterisation backward in its data gradient's reduce, then the heads; their data
+        // gradient's audio columns in the encoder's NHWC order (gA), the text columns in gX_
+        HLMC_TRY(this->z_bwd(s, AT(gS_), ldS, AT(Z_), ldZ, B, L, dfc_w, dfc_b, AF(lv_), AF(eps_), a.d_mu, a.d_logvar,
+                             AT(gml_), ldG));
+        const ops::NhwcOut no{gA, F, (H / 64) * (W / 64), 512};
+        HLMC_TRY(this->heads_bwd(s, AT(gml_), ldG, AT(X_), ldX, B, L, mu_w, mu_b, lv_w, lv_b, AT(gX_), ldX, nullptr, &no));
         // text encoder
         HLMC_TRY(this->bn_bwd(s, AT(gX_) + F, ldX, AT(te_y), B, 256, te_bb, te_g, te_beta, 0, nullptr, 1.f, AT(gt3_), te_b));
         HLMC_TRY(this->lin_bwd(s, AT(gt3_), 256, AT(tin_), ldT, B, te_w, -1, nullptr, 0));
         HLMC_TRY(this->mark(s, 1));
         // audio encoder
-        HLMC_TRY(ops::flat_to_nhwc<T>(s, AT(gX_), ldX, B, H / 64, W / 64, 512, gA));
         HLMC_TRY(this->enc_bwd(s, B, gA, 2));
         HLMC_TRY(this->finish_backward(s));
         return this->mark(s, 3);

@@ -331,6 +331,84 @@ struct StoreReluBwd : StoreRM<OutT> {
     }
 };
 
+// StoreRM for a dense layer whose first ncut output columns are an NCHW-flat map (FlatIdx) that the next kernel reads
+// in NHWC order: column n < ncut of row m goes to nhwc[fx.nhwc(m, n)], the other columns row-major to out as in
+// StoreRM.  Bias, activation and accumulate are indexed by the un-permuted column.  The "row offset" handed from
+// quad() / row_off() to put() is the row index.
+template <typename OutT>
+struct StoreFlatAsNhwc : StoreRM<OutT> {
+    OutT* nhwc;
+    int ncut;
+    FlatIdx fx;
+    struct Row {
+        int m;
+    };
+    struct Quad {
+        int64_t off;
+    };
+    __device__ OutT* at(int m, int n) const {
+        return n < ncut ? nhwc + fx.nhwc(m, n) : this->out + (int64_t)m * this->ld + n;
+    }
+    __device__ Quad quad(int m) const { return Quad{m}; }
+    __device__ int64_t row_off(const Quad& q, int r) const { return q.off + r; }
+    __device__ float put(int64_t ro, int n, float v) const {
+        if (this->act == 1) v = v > 0.f ? v : 0.f;
+        OutT* o = at((int)ro, n);
+        if (this->accumulate) v += to_f32<OutT>(*o);
+        const OutT t = from_f32<OutT>(v);
+        *o = t;
+        return to_f32<OutT>(t);
+    }
+    __device__ void put4(int64_t ro, int n, float (&v)[4]) const {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = put(ro, n + k, v[k]);
+    }
+    __device__ Row row(int m) const { return Row{m}; }
+    __device__ void store(const Row& rw, int n, float v) const {
+        if (this->bias) v += this->bias[n];
+        put(rw.m, n, v);
+    }
+};
+
+// The opposite direction: a conv's NHWC output (row m = (image, pixel), N = fx.C channels) stored as the NCHW-flat
+// rows of the dense layer that reads it, out[fx.flat(m, n)] (+ bias; no activation / accumulate).  relu_ref (nullable):
+// the NHWC post-ReLU map the value is a gradient of; the stored value is zeroed where it is not positive.
+template <typename OutT>
+struct StoreNhwcAsFlat : StoreRM<OutT> {
+    const OutT* relu_ref;
+    FlatIdx fx;
+    struct Row {
+        int m;
+        int64_t base;
+    };
+    struct Quad {
+        int64_t off;
+    };
+    __device__ Quad quad(int m) const { return Quad{m}; }
+    __device__ int64_t row_off(const Quad& q, int r) const { return q.off + r; }
+    __device__ float put_at(int m, int64_t base, int n, float v) const {
+        if (relu_ref && !(to_f32<OutT>(relu_ref[(int64_t)m * fx.C + n]) > 0.f)) v = 0.f;
+        const OutT t = from_f32<OutT>(v);
+        this->out[base + (int64_t)n * fx.hw] = t;
+        return to_f32<OutT>(t);
+    }
+    __device__ float put(int64_t ro, int n, float v) const { return put_at((int)ro, fx.flat_row((int)ro), n, v); }
+    __device__ void put4(int64_t ro, int n, float (&v)[4]) const {
+        const int64_t base = fx.flat_row((int)ro);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = put_at((int)ro, base, n + k, v[k]);
+    }
+    __device__ float stored(int n, float v) const {
+        if (this->bias) v += this->bias[n];
+        return to_f32<OutT>(from_f32<OutT>(v));
+    }
+    __device__ Row row(int m) const { return Row{m, fx.flat_row(m)}; }
+    __device__ void store(const Row& rw, int n, float v) const {
+        if (this->bias) v += this->bias[n];
+        put_at(rw.m, rw.base, n, v);
+    }
+};
+
 // Sub-pixel phase store into a high-res NHWC map [B, 2Hi, 2Wi, N]; m = (b, r, c) over the low grid.
 template <typename OutT>
 struct StoreSubpixel {

@@ -165,6 +165,22 @@ size_t nt_ws(int M, int N, int Kmax, int phases, int BK) {
     return pl.S == 1 ? 0 : (size_t)phases * pl.S * M * N * sizeof(float);
 }
 
+// launch_nt's GEMM to the fp32 partial slabs alone, under the same plan (S = 1: one slab); the caller reduces them.
+// Register path, per-element epilogue (the dense layers' launches: arbitrary ld / K).
+template <typename T, int BM, int BN, int WM, int WN, class AL, class BL>
+int launch_nt_partials(hipStream_t s, const AL& al, const BL& bl, int M, int N, int K, Ws ws, int* S_out) {
+    constexpr int BK = gemm_bk<T>();
+    const int tmn = cdiv(M, BM) * cdiv(N, BN);
+    const Plan pl = plan_nt(tmn, K, BK);
+    HLMC_CHECK_ARG(ws.p && ws.bytes >= (size_t)pl.S * M * N * sizeof(float), "split-K workspace too small");
+    StorePartialZ part;
+    part.ws = ws.p; part.M = M; part.N = N; part.S = pl.S; part.phase = 0; part.split = 0;
+    nt_kernel_launch_tr<T, BM, BN, WM, WN, false>(s, dim3(tmn, 1, pl.S), al, bl, part, M, N, pl.ksl, K >= 1024, 0);
+    HLMC_LAUNCHED();
+    *S_out = pl.S;
+    return HLMC_OK;
+}
+
 // Tile choice for the NT family by N: 128x128 / 128x64 / 128x32.  (Measured: stepping down to 64x64 to put
 // two blocks on every CU doubles operand re-reads and is slower on every layer of the step.)
 inline int nt_tile(int M, int N, int phases) {
@@ -899,8 +915,9 @@ bool subpixel_takes_input_bn(int B, int Hi, int Wi, int Ci, int Co) {
 
 template <typename T>
 int conv_s2(hipStream_t s, const T* x, int B, int Hi, int Wi, int Ci, const T* wp, const float* bias, int Co, T* y, Ws ws,
-            ColStats* st, const BnInput* xin) {
+            ColStats* st, const BnInput* xin, const FlatOut* fo) {
     HLMC_CHECK_ARG(!xin || conv_s2_takes_input_bn<T>(B, Hi, Wi, Ci, Co), "conv_s2: input BatchNorm needs a halo shape");
+    HLMC_CHECK_ARG(!fo || (!st && !xin), "conv_s2: a flat output with fused statistics / input BatchNorm");
     if (xin) HLMC_CHECK_ARG(xin->acc.p && xin->acc.ncols == 2 * Ci && xin->a_out && st && st->acc.on(),
                             "conv_s2: input BatchNorm arguments");
     constexpr int V = Vec16<T>::N;
@@ -912,6 +929,14 @@ int conv_s2(hipStream_t s, const T* x, int B, int Hi, int Wi, int Ci, const T* w
     StoreRM<T> ep{y, bias, Co, 0, 0};
     probe::site(probe::kConvS2, 2.0 * M * Co * K,
                 (double)sizeof(T) * ((double)B * Hi * Wi * Ci + (double)Co * K + (double)M * Co));
+    if (fo) {  // NCHW-flat rows for the dense layer that reads the map (the decoder's first layer's data gradient)
+        HLMC_CHECK_ARG(fo->ld >= Co * Ho * Wo, "conv_s2: flat row stride");
+        StoreNhwcAsFlat<T> ef;
+        static_cast<StoreRM<T>&>(ef) = ep;
+        ef.relu_ref = static_cast<const T*>(fo->relu_ref);
+        ef.fx = FlatIdx(Ho * Wo, Co, fo->ld);
+        return dispatch_nt<T>(s, al, bl, ef, M, Co, K, 1, ws, nullptr);
+    }
     if constexpr (std::is_same<T, bf16>::value) {
         int which;
         conv_halo_shape(Ci, Co, Wi, Hi, which);
@@ -1053,7 +1078,7 @@ size_t wgrad_s2_ws(int B, int Hl, int Wl, int M, int C) {
 
 template <typename T, typename OutT>
 int linear(hipStream_t s, const T* x, int ldx, int M, int K, const T* w, int ldw, const float* bias, int N, OutT* y,
-           int ldy, int act, int accumulate, Ws ws, const OutT* relu_ref) {
+           int ldy, int act, int accumulate, Ws ws, const OutT* relu_ref, const NhwcOut* no) {
     constexpr int V = Vec16<T>::N;
     bool vx = (ldx % V == 0) && aligned16(x);
     bool vw = (ldw % V == 0) && aligned16(w);
@@ -1061,6 +1086,15 @@ int linear(hipStream_t s, const T* x, int ldx, int M, int K, const T* w, int ldw
     DenseLoader<T> bl{w, ldw, N, K, vw};
     StoreRM<OutT> ep{y, bias, ldy, act, accumulate};
     probe::site(probe::kLinear, 2.0 * M * N * K, (double)sizeof(T) * ((double)M * K + (double)N * K) + (double)sizeof(OutT) * M * N);
+    if (no) {  // the first ncut columns in NHWC order for the conv that reads them
+        HLMC_CHECK_ARG(!relu_ref && no->nhwc && no->ncut == no->hw * no->C && no->ncut <= N, "linear: NHWC output");
+        StoreFlatAsNhwc<OutT> en;
+        static_cast<StoreRM<OutT>&>(en) = ep;
+        en.nhwc = static_cast<OutT*>(no->nhwc);
+        en.ncut = no->ncut;
+        en.fx = FlatIdx(no->hw, no->C, 0);
+        return dispatch_linear<T>(s, al, bl, en, M, N, K, ws);
+    }
     if (relu_ref) {
         HLMC_CHECK_ARG(act == 0, "linear: a ReLU-backward mask and a forward activation together");
         StoreReluBwd<OutT> em;
@@ -1073,6 +1107,21 @@ int linear(hipStream_t s, const T* x, int ldx, int M, int K, const T* w, int ldw
 template <typename T>
 size_t linear_ws(int M, int K, int N) {
     return dispatch_linear_ws<T>(M, N, K);
+}
+
+template <typename T>
+int linear_partials(hipStream_t s, const T* x, int ldx, int M, int K, const T* w, int ldw, int N, Ws ws, int* S_out) {
+    constexpr int V = Vec16<T>::N;
+    DenseLoader<T> al{x, ldx, M, K, (ldx % V == 0) && aligned16(x)};
+    DenseLoader<T> bl{w, ldw, N, K, (ldw % V == 0) && aligned16(w)};
+    probe::site(probe::kLinear, 2.0 * M * N * K, (double)sizeof(T) * ((double)M * K + (double)N * K) + 4.0 * M * N);
+    // dispatch_linear's tiles and plan
+    if (M >= 1024 && N >= 128) return launch_nt_partials<T, 128, 128, 64, 64>(s, al, bl, M, N, K, ws, S_out);
+    return launch_nt_partials<T, 64, 64, 32, 32>(s, al, bl, M, N, K, ws, S_out);
+}
+template <typename T>
+size_t linear_partials_ws(int M, int K, int N) {
+    return std::max(dispatch_linear_ws<T>(M, N, K), (size_t)M * N * sizeof(float));
 }
 
 // Final epilogue of a dense weight gradient whose H operand carries the ones column: C[n][k < K] -> dW[n][k],
@@ -1105,6 +1154,38 @@ int linear_wgrad(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int 
     StoreRM<float> ep{dW, nullptr, K, 0, 0};
     return dispatch_tn<T>(s, ll, hl, ep, N, K, Mb, ws);
 }
+// StoreWgradBias for two layers stacked along n (the latent heads' one weight-gradient GEMM): rows n < N1 belong to
+// the first layer, the others to the second (their gradients are not adjacent in the flat gradient)
+struct StoreWgradBiasPair {
+    static constexpr bool kDirectTn = true;
+    float *dW1, *db1, *dW2, *db2;
+    int K, N1;
+    struct Row {
+        float* r;
+        float* b;
+    };
+    __device__ void set_phase(int) {}
+    __device__ Row row(int m) const {
+        return m < N1 ? Row{dW1 + (int64_t)m * K, db1 + m} : Row{dW2 + (int64_t)(m - N1) * K, db2 + (m - N1)};
+    }
+    __device__ void store(const Row& rw, int n, float v) const {
+        if (n < K) rw.r[n] = v;
+        else *rw.b = v;
+    }
+};
+
+template <typename T>
+int linear_wgrad_pair(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int Mb, int N1, int K, float* dW1,
+                      float* db1, float* dW2, float* db2, Ws ws) {
+    constexpr int V = Vec16<T>::N;
+    HLMC_CHECK_ARG(dW1 && db1 && dW2 && db2, "linear_wgrad_pair: gradients required");
+    const int N = 2 * N1;
+    KRowDense<T> ll{dy, lddy, Mb, N, (lddy % V == 0) && aligned16(dy), false};
+    KRowDense<T> hl{x, ldx, Mb, K, (ldx % V == 0) && aligned16(x), true};
+    probe::site(probe::kLinearWgrad, 2.0 * N * K * Mb, (double)sizeof(T) * ((double)Mb * N + (double)Mb * K) + 4.0 * N * K);
+    return dispatch_tn<T>(s, ll, hl, StoreWgradBiasPair{dW1, db1, dW2, db2, K, N1}, N, K + 1, Mb, ws);
+}
+
 template <typename T>
 size_t linear_wgrad_ws(int Mb, int N, int K) {  // with or without the bias column
     return std::max(dispatch_tn_ws<T>(N, K, Mb), dispatch_tn_ws<T>(N, K + 1, Mb));
@@ -1112,7 +1193,7 @@ size_t linear_wgrad_ws(int Mb, int N, int K) {  // with or without the bias colu
 
 #define INST(T)                                                                                                     \
     template int conv_s2<T>(hipStream_t, const T*, int, int, int, int, const T*, const float*, int, T*, Ws,         \
-                            ColStats*, const BnInput*);                                                  \
+                            ColStats*, const BnInput*, const FlatOut*);                                             \
     template bool conv_s2_takes_input_bn<T>(int, int, int, int, int);                                              \
     template bool subpixel_takes_input_bn<T>(int, int, int, int, int);                                             \
     template size_t conv_s2_ws<T>(int, int, int, int, int);                                                        \
@@ -1122,8 +1203,12 @@ size_t linear_wgrad_ws(int Mb, int N, int K) {  // with or without the bias colu
     template int wgrad_s2<T>(hipStream_t, const T*, int, int, int, int, const T*, int, float*, Ws, XAcc, float*);  \
     template size_t wgrad_s2_ws<T>(int, int, int, int, int);                                                       \
     template int linear<T, T>(hipStream_t, const T*, int, int, int, const T*, int, const float*, int, T*, int, int, \
-                              int, Ws, const T*);                                                                  \
+                              int, Ws, const T*, const NhwcOut*);                                                  \
     template size_t linear_ws<T>(int, int, int);                                                                   \
+    template int linear_partials<T>(hipStream_t, const T*, int, int, int, const T*, int, int, Ws, int*);           \
+    template size_t linear_partials_ws<T>(int, int, int);                                                          \
+    template int linear_wgrad_pair<T>(hipStream_t, const T*, int, const T*, int, int, int, int, float*, float*,    \
+                                      float*, float*, Ws);                                                         \
     template int linear_wgrad<T>(hipStream_t, const T*, int, const T*, int, int, int, int, float*, float*, Ws);    \
     template size_t linear_wgrad_ws<T>(int, int, int);
 
@@ -1131,7 +1216,7 @@ INST(float)
 INST(bf16)
 #undef INST
 template int linear<bf16, float>(hipStream_t, const bf16*, int, int, int, const bf16*, int, const float*, int, float*,
-                                 int, int, int, Ws, const float*);
+                                 int, int, int, Ws, const float*, const NhwcOut*);
 
 }  // namespace ops
 }  // namespace hlmc

@@ -248,12 +248,13 @@ struct BnChan {  // one thread's V channels of BatchNorm parameters
 
 // a = act(gamma*(y-mean)*invstd + beta) [* mask * mscale]; grid-stride over row passes.
 // kFin: train mode, mean / invstd folded here from the partial table (bn_fin_prologue).
-template <typename T, bool kMask, bool kFin>
+// kFlat: the NHWC map is stored NCHW-flat through fx (the encoder's last activation, read by a dense layer).
+template <typename T, bool kMask, bool kFin, bool kFlat = false>
 __global__ __launch_bounds__(256) void bn_act_kernel(const T* __restrict__ y, int64_t R, int C,
                                                      const float* __restrict__ mean, const float* __restrict__ invstd,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      int act, const uint8_t* __restrict__ mask, float mscale,
-                                                     T* __restrict__ a, int lda, BnFin fin) {
+                                                     T* __restrict__ a, int lda, BnFin fin, FlatIdx fx = FlatIdx()) {
     constexpr int V = Vec16<T>::N;
     __shared__ double fin_sh[kFin ? 2 * kFinMaxC + 3 * kThreads : 1];  // totals | fold scratch
     __shared__ float fin_x[kFin ? 2 * kFinMaxC : 1];                     // mean | invstd
@@ -295,7 +296,13 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const T* __restrict__ y, in
                 if constexpr (kMask) t = mask[ru * C + c0 + v] ? t * mscale : 0.f;
                 o[v] = t;
             }
-            store16_f32(a + ru * lda + c0, o);
+            if constexpr (kFlat) {
+                T* d = a + fx.flat((int)ru, c0);
+#pragma unroll
+                for (int v = 0; v < V; ++v) d[(int64_t)v * fx.hw] = from_f32<T>(o[v]);
+            } else {
+                store16_f32(a + ru * lda + c0, o);
+            }
         }
     }
 }
@@ -1203,30 +1210,6 @@ __global__ void cast2d_kernel(const TI* __restrict__ x, int ldx, TO* __restrict_
         y[(int64_t)r * ldy + c] = from_f32<TO>(to_f32<TI>(x[(int64_t)r * ldx + c]));
     }
 }
-template <typename T>
-__global__ void nhwc_to_flat_kernel(const T* __restrict__ x, int B, int h, int w, int C, T* __restrict__ y, int ldy,
-                                    const T* __restrict__ relu_ref) {
-    const int F = C * h * w;
-    int64_t n = (int64_t)B * F;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        int b = (int)(i / F), f = (int)(i % F);
-        int c = f / (h * w), hw = f % (h * w);
-        const int64_t o = (int64_t)b * ldy + f;
-        T v = x[((int64_t)b * h * w + hw) * C + c];
-        if (relu_ref && !(to_f32<T>(relu_ref[o]) > 0.f)) v = from_f32<T>(0.f);
-        y[o] = v;
-    }
-}
-template <typename T>
-__global__ void flat_to_nhwc_kernel(const T* __restrict__ x, int ldx, int B, int h, int w, int C, T* __restrict__ y) {
-    const int F = C * h * w;
-    int64_t n = (int64_t)B * F;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        int b = (int)(i / F), rem = (int)(i % F);
-        int hw = rem / C, c = rem % C;  // i enumerates the NHWC output
-        y[i] = x[(int64_t)b * ldx + (int64_t)c * h * w + hw];
-    }
-}
 // optional copies a reparameterisation launch also writes: the caller's mu / logvar outputs and (host-supplied eps)
 // the eps the backward keeps -- one launch instead of a copy launch plus the reparameterisation
 struct LatentOut {
@@ -1324,6 +1307,86 @@ __global__ void reparam_bwd_kernel(const T* __restrict__ dz, int lddz, const flo
         float sd = expf(0.5f * lv[i]);
         gmu[i] = from_f32<T>((d_mu ? d_mu[i] : 0.f) + g);
         glv[i] = from_f32<T>((d_lv ? d_lv[i] : 0.f) + g * eps[i] * sd * 0.5f);
+    }
+}
+
+// The latent heads' split-K reduce with the reparameterisation in its store (ops.hpp heads_reparam).  part: S slabs
+// [n_rows][2L] (fc_mu's columns, then fc_logvar's).  One thread per group of 4 consecutive elements of the [n_rows][L]
+// latent block, as reparam_rng_kernel: element i draws stream element offset + i.
+template <typename T, bool kVec4>
+__global__ void heads_reparam_kernel(const float* __restrict__ part, int S, int n_rows, int L,
+                                     const float* __restrict__ mu_bias, const float* __restrict__ lv_bias,
+                                     float* __restrict__ mu, float* __restrict__ lv, LatentOut lo,
+                                     const float* __restrict__ eps_in, uint64_t seed, uint64_t offset,
+                                     T* __restrict__ z, int ldz) {
+    const int64_t n = (int64_t)n_rows * L, groups = (n + 3) / 4;
+    const int64_t st = 2 * n;  // one slab
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < groups; t += (int64_t)gridDim.x * blockDim.x) {
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (z && !eps_in) philox_normal4(seed, offset / 4 + t, v);
+        // L % 4 == 0 (kVec4): the group is 4 consecutive columns of one row, summed with 16-byte slab loads (all
+        // 2 S of them independent); else element by element.  Either way ascending split order per element, as
+        // splitk_reduce_kernel.
+        float ms[4] = {0.f, 0.f, 0.f, 0.f}, ls[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (kVec4) {
+            const int r = (int)(4 * t / L), c = (int)(4 * t - (int64_t)r * L);
+            const float* p = part + (int64_t)r * 2 * L + c;
+#pragma unroll 4
+            for (int k = 0; k < S; ++k) {
+                const float4 a = *reinterpret_cast<const float4*>(p + k * st);
+                const float4 b = *reinterpret_cast<const float4*>(p + k * st + L);
+                ms[0] += a.x; ms[1] += a.y; ms[2] += a.z; ms[3] += a.w;
+                ls[0] += b.x; ls[1] += b.y; ls[2] += b.z; ls[3] += b.w;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t i = 4 * t + j;
+            if (i >= n) break;
+            const int r = (int)(i / L), c = (int)(i - (int64_t)r * L);
+            float m = ms[j], l = ls[j];
+            if constexpr (!kVec4) {
+                const float* p = part + (int64_t)r * 2 * L + c;
+#pragma unroll 4
+                for (int k = 0; k < S; ++k) {
+                    m += p[k * st];
+                    l += p[k * st + L];
+                }
+            }
+            m += mu_bias[c];
+            l += lv_bias[c];
+            mu[i] = m;
+            lv[i] = l;
+            if (lo.mu) lo.mu[i] = m;
+            if (lo.lv) lo.lv[i] = l;
+            if (z) {
+                const float e = eps_in ? eps_in[i] : v[j];
+                lo.eps[i] = e;
+                z[(int64_t)r * ldz + c] = from_f32<T>(m + e * expf(0.5f * l));
+            }
+        }
+    }
+}
+
+// The split-K reduce of decoder_input's data gradient with reparam_bwd_kernel's arithmetic in its store (ops.hpp
+// reparam_bwd_reduce).  dz is rounded to T as the data gradient's own store would round it, so the step computes what
+// the two separate launches (reduce to T, then reparam_bwd_kernel) compute, bit for bit.  part: S slabs [n_rows][L].
+template <typename T>
+__global__ void reparam_bwd_reduce_kernel(const float* __restrict__ part, int S, int n_rows, int L,
+                                          const float* __restrict__ lv, const float* __restrict__ eps,
+                                          const float* __restrict__ d_mu, const float* __restrict__ d_lv,
+                                          T* __restrict__ gmu, T* __restrict__ glv, int ldg) {
+    const int64_t n = (int64_t)n_rows * L;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / L), c = (int)(i - (int64_t)r * L);
+        float g = 0.f;
+#pragma unroll 4
+        for (int k = 0; k < S; ++k) g += part[k * n + i];
+        g = to_f32<T>(from_f32<T>(g));
+        const float sd = expf(0.5f * lv[i]);
+        const int64_t o = (int64_t)r * ldg + c;
+        gmu[o] = from_f32<T>((d_mu ? d_mu[i] : 0.f) + g);
+        glv[o] = from_f32<T>((d_lv ? d_lv[i] : 0.f) + g * eps[i] * sd * 0.5f);
     }
 }
 
@@ -1611,6 +1674,12 @@ static int check_bn_shape(int C) {
     HLMC_CHECK_ARG(C % V == 0 && C / V <= 256 && 256 % (C / V) == 0, "BatchNorm channel count unsupported");
     return HLMC_OK;
 }
+static int check_flat_out(const FlatOut* fo, int hw, int64_t R, int C, const uint8_t* mask) {
+    if (!fo) return HLMC_OK;
+    HLMC_CHECK_ARG(!mask && !fo->relu_ref, "bn_act: a flat output takes no mask");
+    HLMC_CHECK_ARG(hw > 0 && R % hw == 0 && R < 2147483647 && fo->ld >= (int64_t)C * hw, "bn_act: flat output shape");
+    return HLMC_OK;
+}
 static int check_acc(const XAcc& a, int ncols) {
     HLMC_CHECK_ARG(a.p && a.ncols == ncols && a.shards >= 1 && a.shards <= kXAccMaxShards, "statistics accumulator");
     return HLMC_OK;
@@ -1648,13 +1717,18 @@ int bn_eval_stats(hipStream_t s, const float* run_mean, const float* run_var, in
 
 template <typename T>
 int bn_act(hipStream_t s, const T* y, int64_t R, int C, const float* mean, const float* invstd, const float* gamma,
-           const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda) {
+           const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda, const FlatOut* fo, int hw) {
     HLMC_TRY(check_bn_shape<T>(C));
-    HLMC_CHECK_ARG(lda % Vec16<T>::N == 0, "bn_act: output row stride must be a multiple of 16 bytes");
+    HLMC_CHECK_ARG(fo || lda % Vec16<T>::N == 0, "bn_act: output row stride must be a multiple of 16 bytes");
+    HLMC_TRY(check_flat_out(fo, hw, R, C, mask));
     const int rpp = kThreads / (C / Vec16<T>::N);
     const unsigned g = grid_for(R, rpp * kU);
     const double by = 2.0 * sizeof(T) * R * C;
-    if (mask)
+    if (fo)
+        HLMC_BN_PROBED(s, by, (bn_act_kernel<T, false, false, true><<<g, kThreads, 0, s>>>(
+                                  y, R, C, mean, invstd, gamma, beta, act, mask, mscale, a, lda, BnFin{},
+                                  FlatIdx(hw, C, fo->ld))));
+    else if (mask)
         HLMC_BN_PROBED(s, by, (bn_act_kernel<T, true, false><<<g, kThreads, 0, s>>>(y, R, C, mean, invstd, gamma, beta, act,
                                                                                    mask, mscale, a, lda, BnFin{})));
     else
@@ -1667,10 +1741,12 @@ int bn_act(hipStream_t s, const T* y, int64_t R, int C, const float* mean, const
 template <typename T>
 int bn_act_train(hipStream_t s, const T* y, int64_t R, int C, XAcc acc, bool have_stats, float* mean, float* invstd,
                  float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, const float* gamma,
-                 const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda) {
+                 const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda, const FlatOut* fo,
+                 int hw) {
     HLMC_TRY(check_bn_shape<T>(C));
     HLMC_TRY(check_acc(acc, 2 * C));
-    HLMC_CHECK_ARG(lda % Vec16<T>::N == 0, "bn_act: output row stride must be a multiple of 16 bytes");
+    HLMC_CHECK_ARG(fo || lda % Vec16<T>::N == 0, "bn_act: output row stride must be a multiple of 16 bytes");
+    HLMC_TRY(check_flat_out(fo, hw, R, C, mask));
     if (!have_stats) {  // no statistics from the producer: a moments pass into the (zeroed) accumulator first
         HLMC_BN_PROBED(s, (double)sizeof(T) * R * C,
                        (col_moments_kernel<T><<<bn_blocks(R, C), kThreads, 0, s>>>(y, R, C, bn_rows_per_blk(R, C), acc)));
@@ -1679,7 +1755,7 @@ int bn_act_train(hipStream_t s, const T* y, int64_t R, int C, XAcc acc, bool hav
     if (C > kFinMaxC) {  // wide channels: a separate finalize
         bn_finalize_kernel<<<fin_grid(C), 64, 0, s>>>(acc, C, R, mean, invstd, run_mean, run_var, nbt, momentum, eps);
         HLMC_LAUNCHED();
-        return bn_act<T>(s, y, R, C, mean, invstd, gamma, beta, act, mask, mscale, a, lda);
+        return bn_act<T>(s, y, R, C, mean, invstd, gamma, beta, act, mask, mscale, a, lda, fo, hw);
     }
     BnFin fin;
     fin.acc = acc; fin.R = R;
@@ -1688,7 +1764,11 @@ int bn_act_train(hipStream_t s, const T* y, int64_t R, int C, XAcc acc, bool hav
     const int rpp = kThreads / (C / Vec16<T>::N);
     const unsigned g = grid_for(R, rpp * kU);
     const double by = 2.0 * sizeof(T) * R * C;
-    if (mask)
+    if (fo)
+        HLMC_BN_PROBED(s, by, (bn_act_kernel<T, false, true, true><<<g, kThreads, 0, s>>>(
+                                  y, R, C, mean, invstd, gamma, beta, act, mask, mscale, a, lda, fin,
+                                  FlatIdx(hw, C, fo->ld))));
+    else if (mask)
         HLMC_BN_PROBED(s, by, (bn_act_kernel<T, true, true><<<g, kThreads, 0, s>>>(y, R, C, mean, invstd, gamma, beta, act,
                                                                                   mask, mscale, a, lda, fin)));
     else
@@ -1987,18 +2067,6 @@ int cast2d_from_f32(hipStream_t s, const float* x, int ldx, T* y, int ldy, int r
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
-template <typename T>
-int nhwc_to_flat(hipStream_t s, const T* x, int B, int h, int w, int C, T* y, int ldy, const T* relu_ref) {
-    nhwc_to_flat_kernel<T><<<grid_for((int64_t)B * C * h * w), kThreads, 0, s>>>(x, B, h, w, C, y, ldy, relu_ref);
-    HLMC_LAUNCHED();
-    return HLMC_OK;
-}
-template <typename T>
-int flat_to_nhwc(hipStream_t s, const T* x, int ldx, int B, int h, int w, int C, T* y) {
-    flat_to_nhwc_kernel<T><<<grid_for((int64_t)B * C * h * w), kThreads, 0, s>>>(x, ldx, B, h, w, C, y);
-    HLMC_LAUNCHED();
-    return HLMC_OK;
-}
 static int colsum_blocks(int rows) { return std::max(1, std::min(1024, rows / 256)); }
 size_t colsum_ws(int rows, int cols) { return (size_t)colsum_blocks(rows) * cols * sizeof(double); }  // <= 1024 rows: no fold
 template <typename T>
@@ -2102,6 +2170,35 @@ int reparam_bwd(hipStream_t s, const T* dz, int lddz, const float* lv, const flo
                 const float* d_lv, int n_rows, int L, T* gmu, T* glv) {
     reparam_bwd_kernel<T><<<grid_for((int64_t)n_rows * L), kThreads, 0, s>>>(dz, lddz, lv, eps, d_mu, d_lv, n_rows, L,
                                                                             gmu, glv);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
+}
+template <typename T>
+int heads_reparam(hipStream_t s, const float* part, int S, int n_rows, int L, const float* mu_bias,
+                  const float* lv_bias, float* mu, float* lv, float* mu_out, float* lv_out, const float* eps_in,
+                  uint64_t seed, uint64_t offset, float* eps_keep, T* z, int ldz) {
+    HLMC_CHECK_ARG(part && S >= 1 && n_rows > 0 && L > 0 && mu_bias && lv_bias && mu && lv, "heads_reparam: arguments");
+    HLMC_CHECK_ARG(!z || (eps_keep && ldz >= L), "heads_reparam: z needs eps_keep and ldz >= L");
+    HLMC_CHECK_ARG(offset % 4 == 0, "heads_reparam: offset must be a multiple of 4");
+    LatentOut lo;
+    lo.mu = mu_out; lo.lv = lv_out; lo.eps = eps_keep;
+    const unsigned g = grid_for(((int64_t)n_rows * L + 3) / 4, 64);  // 64-thread blocks: B * L / 4 groups are few
+    if (L % 4 == 0 && ((uintptr_t)part & 15) == 0)
+        heads_reparam_kernel<T, true><<<g, 64, 0, s>>>(part, S, n_rows, L, mu_bias, lv_bias, mu, lv, lo, eps_in, seed,
+                                                       offset, z, ldz);
+    else
+        heads_reparam_kernel<T, false><<<g, 64, 0, s>>>(part, S, n_rows, L, mu_bias, lv_bias, mu, lv, lo, eps_in, seed,
+                                                        offset, z, ldz);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
+}
+template <typename T>
+int reparam_bwd_reduce(hipStream_t s, const float* part, int S, int n_rows, int L, const float* lv, const float* eps,
+                       const float* d_mu, const float* d_lv, T* gmu, T* glv, int ldg) {
+    HLMC_CHECK_ARG(part && S >= 1 && n_rows > 0 && L > 0 && lv && eps && gmu && glv && ldg >= L,
+                   "reparam_bwd_reduce: arguments");
+    reparam_bwd_reduce_kernel<T><<<grid_for((int64_t)n_rows * L), kThreads, 0, s>>>(part, S, n_rows, L, lv, eps, d_mu,
+                                                                                   d_lv, gmu, glv, ldg);
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
@@ -2210,10 +2307,10 @@ int pack(hipStream_t s, const AdamJob* jobs_dev, int njobs, int total_tiles) {
                              float, XAcc);                                                                            \
     template int bn_moments<T>(hipStream_t, const T*, int64_t, int, XAcc);                                             \
     template int bn_act<T>(hipStream_t, const T*, int64_t, int, const float*, const float*, const float*, const float*, \
-                           int, const uint8_t*, float, T*, int);                                                      \
+                           int, const uint8_t*, float, T*, int, const FlatOut*, int);                                 \
     template int bn_act_train<T>(hipStream_t, const T*, int64_t, int, XAcc, bool, float*, float*, float*,            \
                                  float*, int64_t*, float, float, const float*, const float*, int, const uint8_t*, float, \
-                                 T*, int);                                                                           \
+                                 T*, int, const FlatOut*, int);                                                      \
     template int bn_act_bwd<T>(hipStream_t, const T*, int, const T*, int64_t, int, const float*, const float*,          \
                                const float*, const float*, int, const uint8_t*, float, T*, float*, float*, XAcc,      \
                                const BnBwdFuse*, XAcc, float*, float*);                                              \
@@ -2225,8 +2322,10 @@ int pack(hipStream_t s, const AdamJob* jobs_dev, int njobs, int total_tiles) {
     template int cast_to_f32<T>(hipStream_t, const T*, float*, int64_t);                                             \
     template int copy2d<T>(hipStream_t, const T*, int, T*, int, int, int);                                           \
     template int cast2d_from_f32<T>(hipStream_t, const float*, int, T*, int, int, int);                              \
-    template int nhwc_to_flat<T>(hipStream_t, const T*, int, int, int, int, T*, int, const T*);                      \
-    template int flat_to_nhwc<T>(hipStream_t, const T*, int, int, int, int, int, T*);                                \
+    template int heads_reparam<T>(hipStream_t, const float*, int, int, int, const float*, const float*, float*,      \
+                                  float*, float*, float*, const float*, uint64_t, uint64_t, float*, T*, int);        \
+    template int reparam_bwd_reduce<T>(hipStream_t, const float*, int, int, int, const float*, const float*,         \
+                                       const float*, const float*, T*, T*, int);                                     \
     template int colsum<T>(hipStream_t, const T*, int, int, int, float*, Ws);                                        \
     template int reparam_fwd<T>(hipStream_t, const float*, const float*, const float*, int, int, T*, int, float*,     \
                                 float*, float*);                                                                     \

@@ -47,10 +47,25 @@ template <typename T>
 bool conv_s2_takes_input_bn(int B, int Hi, int Wi, int Ci, int Co);
 template <typename T>
 bool subpixel_takes_input_bn(int B, int Hi, int Wi, int Ci, int Co);
+// The low-res map between the conv stacks and the dense middle is stored by its producer in its consumer's order
+// (common.hpp FlatIdx), so no relayout launch sits between them:
+// FlatOut: an NHWC producer writes the NCHW-flat rows (stride ld) of the dense layer that reads it; relu_ref
+// (nullable): the NHWC post-ReLU map the output is a gradient of (zeroed where that is not positive).
+struct FlatOut {
+    int ld;
+    const void* relu_ref;
+};
+// NhwcOut: a dense layer writes its first ncut output columns (an NCHW-flat [C][hw] map) in NHWC order to nhwc; the
+// remaining columns go to y as usual.
+struct NhwcOut {
+    void* nhwc;
+    int ncut, hw, C;
+};
 // xin (nullable): BnInput (train-mode BatchNorm of the input applied while staging; needs st)
+// fo (nullable): y is written NCHW-flat ([B][fo->ld], column co * Ho * Wo + pixel); not with st / xin
 template <typename T>
 int conv_s2(hipStream_t s, const T* x, int B, int Hi, int Wi, int Ci, const T* wp, const float* bias, int Co, T* y, Ws ws,
-            ColStats* st = nullptr, const BnInput* xin = nullptr);
+            ColStats* st = nullptr, const BnInput* xin = nullptr, const FlatOut* fo = nullptr);
 template <typename T>
 size_t conv_s2_ws(int B, int Hi, int Wi, int Ci, int Co);
 
@@ -72,11 +87,20 @@ size_t wgrad_s2_ws(int B, int Hl, int Wl, int M, int C);
 // y[m*ldy + n] (+)= act(sum_k x[m*ldx+k] * w[n*ldw+k] + bias[n]),  act 0 none / 1 relu
 // relu_ref (nullable, row stride ldy, act == 0): the stored value is zeroed where relu_ref <= 0 — the data gradient
 // of a dense layer with the ReLU backward of the layer below applied in the epilogue (after the accumulate)
+// no (nullable, not with relu_ref): NhwcOut
 template <typename T, typename OutT>
 int linear(hipStream_t s, const T* x, int ldx, int M, int K, const T* w, int ldw, const float* bias, int N, OutT* y,
-           int ldy, int act, int accumulate, Ws ws, const OutT* relu_ref = nullptr);
+           int ldy, int act, int accumulate, Ws ws, const OutT* relu_ref = nullptr, const NhwcOut* no = nullptr);
 template <typename T>
 size_t linear_ws(int M, int K, int N);
+// The GEMM of linear() alone: the fp32 split-K partial slabs ws.p[(split * M + m) * N + n] and *S_out = their
+// count (>= 1: one slab when the plan does not split).  The caller's own reduce launch sums them in ascending split
+// order and applies its epilogue (kernels.hip: heads_reparam, reparam_bwd_reduce) -- always these two launches, so the
+// unsplit case is no separate code path.
+template <typename T>
+int linear_partials(hipStream_t s, const T* x, int ldx, int M, int K, const T* w, int ldw, int N, Ws ws, int* S_out);
+template <typename T>
+size_t linear_partials_ws(int M, int K, int N);
 
 // dW[n][k] = sum_b dy[b*lddy+n] * x[b*ldx+k];  db[n] = sum_b dy[b*lddy+n] (nullable: the same GEMM with a
 // virtual ones column appended to x, so no separate column-sum launches)
@@ -85,6 +109,11 @@ int linear_wgrad(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int 
                  Ws ws);
 template <typename T>
 size_t linear_wgrad_ws(int Mb, int N, int K);
+// The same for two layers that read the same x and whose dy are the column halves [0, N1) / [N1, 2 N1) of one
+// buffer (the latent heads): one GEMM, rows n < N1 to dW1 / db1, the others to dW2 / db2
+template <typename T>
+int linear_wgrad_pair(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int Mb, int N1, int K, float* dW1,
+                      float* db1, float* dW2, float* db2, Ws ws);
 
 // ---------------------------------------------------------------- edge convs with one channel (kernels.hip)
 // y[B,Hi/2,Wi/2,32] = sum_taps x[B,Hi,Wi] * w[co*9+tap] (+ bias)  (conv1 fwd, convT6 dgrad)
@@ -122,10 +151,13 @@ int bn_eval_stats(hipStream_t s, const float* run_mean, const float* run_var, in
 template <typename T>
 int bn_act_train(hipStream_t s, const T* y, int64_t R, int C, XAcc acc, bool have_stats, float* mean, float* invstd,
                  float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, const float* gamma,
-                 const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda);
+                 const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda,
+                 const FlatOut* fo = nullptr, int hw = 0);
+// fo (nullable, no mask): the [R = B * hw][C] NHWC map is written NCHW-flat to a ([B][fo->ld]); lda is unused
 template <typename T>
 int bn_act(hipStream_t s, const T* y, int64_t R, int C, const float* mean, const float* invstd, const float* gamma,
-           const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda);
+           const float* beta, int act, const uint8_t* mask, float mscale, T* a, int lda, const FlatOut* fo = nullptr,
+           int hw = 0);
 // backward through act+BN: dy from da (ld lda); dgamma, dbeta.  mom: zeroed accumulator of the moments (2C
 // columns; fused->done: the producer of da already delivered them there).  bias_acc (may be off): the column sums
 // of dy (the conv bias gradient) are added there; dbias (nullable, needs bias_acc): also reduce them into dbias
@@ -154,11 +186,6 @@ template <typename T> int cast_to_f32(hipStream_t s, const T* x, float* y, int64
 // rows x cols submatrix copy with leading dims (T -> T)
 template <typename T> int copy2d(hipStream_t s, const T* x, int ldx, T* y, int ldy, int rows, int cols);
 template <typename T> int cast2d_from_f32(hipStream_t s, const float* x, int ldx, T* y, int ldy, int rows, int cols);
-// NHWC [B,h,w,C] <-> flat NCHW [B, C*h*w] (ld = row stride of the flat side)
-// relu_ref (nullable, row stride ldy): y zeroed where relu_ref <= 0 (ReLU backward fused into the relayout)
-template <typename T>
-int nhwc_to_flat(hipStream_t s, const T* x, int B, int h, int w, int C, T* y, int ldy, const T* relu_ref = nullptr);
-template <typename T> int flat_to_nhwc(hipStream_t s, const T* x, int ldx, int B, int h, int w, int C, T* y);
 // db[n] = sum_r dy[r*ld + n]
 template <typename T> int colsum(hipStream_t s, const T* dy, int ld, int rows, int cols, float* db, Ws ws);
 size_t colsum_ws(int rows, int cols);
@@ -179,6 +206,22 @@ int reparam_fwd(hipStream_t s, const float* mu, const float* lv, const float* ep
 template <typename T>
 int reparam_bwd(hipStream_t s, const T* dz, int lddz, const float* lv, const float* eps, const float* d_mu,
                 const float* d_lv, int n_rows, int L, T* gmu, T* glv);
+
+// The latent heads' reduce launch (after linear_partials of the paired fc_mu | fc_logvar weight, N = 2L): for each
+// (b, j) sums the S partial slabs of columns j and L + j in ascending split order, adds the biases and writes
+// mu / lv ([B][L] f32) and their copies mu_out / lv_out (nullable).  With z (nullable: encode only) also the
+// reparameterisation: eps from eps_in, or (eps_in null) the Philox stream elements reparam_rng draws (seed, offset,
+// offset % 4 == 0), kept in eps_keep; z = mu + eps * exp(0.5 lv) as T with row stride ldz.
+template <typename T>
+int heads_reparam(hipStream_t s, const float* part, int S, int n_rows, int L, const float* mu_bias,
+                  const float* lv_bias, float* mu, float* lv, float* mu_out, float* lv_out, const float* eps_in,
+                  uint64_t seed, uint64_t offset, float* eps_keep, T* z, int ldz);
+// The reduce launch of decoder_input's data gradient (after linear_partials, N = L): dz = the sum of the S slabs in
+// ascending split order rounded to T (as linear() stores it), then reparam_bwd's arithmetic: gmu[b * ldg + j] = d_mu + dz,
+// glv[b * ldg + j] = d_lv + dz * eps * 0.5 exp(0.5 lv) (d_mu / d_lv nullable: 0)
+template <typename T>
+int reparam_bwd_reduce(hipStream_t s, const float* part, int S, int n_rows, int L, const float* lv, const float* eps,
+                       const float* d_mu, const float* d_lv, T* gmu, T* glv, int ldg);
 
 // ---------------------------------------------------------------- loss (kernels.hip)
 // partial sums: out[0] = sum (ra-a)^2, out[1] = sum (rt-t)^2, out[2] = sum(1 + lv - mu^2 - e^lv)  (double)
