@@ -310,6 +310,16 @@ class KMeans:
                 best = r
         return best
 
+    @staticmethod
+    def _require_finite(Xd):
+        """sklearn's check_array rejects NaN / infinity.  Here it is also what keeps the kernels in bounds: a
+        non-finite centre compares below no distance, the E-step then stores no cluster index and the kernels
+        after it index the centres with the labels unchecked."""
+        if Xd.dim() != 2 or Xd.shape[0] < 1 or Xd.shape[1] < 1:
+            raise ValueError("X must be 2-D [n_samples, n_features] with at least one row and one column")
+        if not bool(torch.isfinite(Xd).all()):
+            raise ValueError("Input X contains NaN or infinity.")
+
     # ------------------------------------------------------------------ sklearn API
     def fit(self, X, y=None, sample_weight=None):
         if sample_weight is not None:
@@ -317,6 +327,7 @@ class KMeans:
         dev = self._dev()
         Xd = torch.as_tensor(np.asarray(X, dtype=np.float32) if not torch.is_tensor(X) else X, device=dev)
         Xd = Xd.to(torch.float32).contiguous()
+        self._require_finite(Xd)
         n, d = Xd.shape
         if n < self.n_clusters:
             raise ValueError(f"n_samples={n} should be >= n_clusters={self.n_clusters}")
@@ -359,7 +370,10 @@ class KMeans:
         dev = self._dev()
         Xd = torch.as_tensor(np.asarray(X, dtype=np.float32) if not torch.is_tensor(X) else X, device=dev)
         Xd = Xd.to(torch.float32).contiguous()
+        self._require_finite(Xd)
         n, d = Xd.shape
+        if d != self.cluster_centers_.shape[1]:
+            raise ValueError(f"X has {d} features, but KMeans was fitted with {self.cluster_centers_.shape[1]}")
         C_ = torch.as_tensor(self.cluster_centers_, device=dev).contiguous()
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         L.check(L.lib().hlmc_km_assign(L.stream(), Xd.data_ptr(), n, d, C_.data_ptr(), self.n_clusters,

@@ -806,6 +806,7 @@ int center(hipStream_t s, const float* X, int64_t n, int d, float* mean, float* 
 
 int sqdist_rows(hipStream_t s, const float* X, int64_t n, int d, const int64_t* cand, int ncand, float* out) {
     HLMC_CHECK_ARG(X && cand && out && ncand >= 1 && ncand <= 16 && d <= 512, "bad km_sqdist_rows arguments");
+    HLMC_CHECK_ARG(n > 0 && d > 0, "bad km_sqdist_rows sizes");
     Cand c{};
     c.n = ncand;
     for (int t = 0; t < ncand; ++t) {
@@ -891,8 +892,9 @@ int update_batch(hipStream_t s, int k, int d, int R, uint64_t active, const floa
 
 int pp_search(hipStream_t s, int64_t n, int R, int T, const float* prev, int prevT, const int32_t* best,
               const double* rvals, int64_t* cand, int32_t* amb) {
-    HLMC_CHECK_ARG(prev && best && rvals && cand && amb && n > 0 && R >= 1 && T >= 1 && R * T <= kPpMax && prevT >= 1,
-                   "bad km_pp_search arguments");
+    HLMC_CHECK_ARG(prev && best && rvals && cand && amb && n > 0 && prevT >= 1, "bad km_pp_search arguments");
+    HLMC_CHECK_ARG(R >= 1 && T >= 1 && R <= kPpMax && T <= kPpMax && R * T <= kPpMax,
+                   "km_pp_search: restarts x trials outside [1, 64]");
     PpArgs a{};
     for (int r = 0; r < R; ++r) {
         HLMC_CHECK_ARG(best[r] >= 0 && best[r] < prevT, "km_pp_search: best row out of range");
@@ -906,7 +908,9 @@ int pp_search(hipStream_t s, int64_t n, int R, int T, const float* prev, int pre
 
 int pp_dist(hipStream_t s, const float* X, int64_t n, int d, int R, int T, const int64_t* cand, const float* prev,
             int prevT, const int32_t* best, float* out) {
-    HLMC_CHECK_ARG(X && cand && out && n > 0 && d > 0 && R >= 1 && T >= 1 && R * T <= kPpMax, "bad km_pp_dist arguments");
+    HLMC_CHECK_ARG(X && cand && out && n > 0 && d > 0, "bad km_pp_dist arguments");
+    HLMC_CHECK_ARG(R >= 1 && T >= 1 && R <= kPpMax && T <= kPpMax && R * T <= kPpMax,
+                   "km_pp_dist: restarts x trials outside [1, 64]");
     const size_t sh = ((size_t)R * T * d + (size_t)R * T) * sizeof(double);
     HLMC_CHECK_ARG(sh <= 160 * 1024, "km_pp_dist: restarts x trials x d too large for LDS");
     PpArgs a{};
@@ -925,7 +929,8 @@ int pp_dist(hipStream_t s, const float* X, int64_t n, int d, int R, int T, const
 
 int inertia_batch(hipStream_t s, const float* X, int64_t n, int d, const float* C, int k, const int32_t* labels, int R,
                   float* out, float* tmp) {
-    HLMC_CHECK_ARG(X && C && labels && out && tmp && R >= 1, "bad km_inertia arguments");
+    HLMC_CHECK_ARG(X && C && labels && out && tmp, "bad km_inertia arguments");
+    HLMC_CHECK_ARG(n > 0 && d > 0 && k > 0 && R >= 1 && R <= 64, "bad km_inertia sizes");
     km_rowdist_kernel<<<dim3((unsigned)std::min<int64_t>(4096, (n + 255) / 256), (unsigned)R), 256, 0, s>>>(
         X, n, d, C, k, labels, tmp);
     HLMC_LAUNCHED();
@@ -939,6 +944,8 @@ int inertia(hipStream_t s, const float* X, int64_t n, int d, const float* C, con
 }
 
 int rowdist(hipStream_t s, const float* X, int64_t n, int d, const float* C, const int32_t* labels, float* out) {
+    HLMC_CHECK_ARG(X && C && labels && out, "bad km_rowdist arguments");
+    HLMC_CHECK_ARG(n > 0 && d > 0, "bad km_rowdist sizes");
     km_rowdist_kernel<<<(unsigned)std::min<int64_t>(4096, (n + 255) / 256), 256, 0, s>>>(X, n, d, C, 1, labels, out);
     HLMC_LAUNCHED();
     return HLMC_OK;

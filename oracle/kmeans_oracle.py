@@ -173,6 +173,30 @@ def _sqdist_upcast(A: np.ndarray, X: np.ndarray) -> np.ndarray:
     return np.maximum(d.astype(np.float32), np.float32(0))
 
 
+def sqdist_exact(A: np.ndarray, X: np.ndarray) -> np.ndarray:
+    """The exact ||a - x||^2 of float32 rows, correctly rounded to float64: per pair math.fsum over the 3d terms
+    -2 a_c x_c, a_c^2, x_c^2, each of which is exact in float64 (a 24-bit x 24-bit product, a power-of-two scale)."""
+    import math
+    A64 = np.asarray(A, f32).astype(np.float64)
+    X64 = np.asarray(X, f32).astype(np.float64)
+    aa, xx = A64 * A64, X64 * X64
+    out = np.empty((A64.shape[0], X64.shape[0]), np.float64)
+    for t in range(A64.shape[0]):
+        terms = np.concatenate([-2.0 * A64[t][None, :] * X64, np.broadcast_to(aa[t], X64.shape), xx], axis=1)
+        out[t] = [max(math.fsum(row), 0.0) for row in terms.tolist()]
+    return out
+
+
+def sqdist_bound(A: np.ndarray, X: np.ndarray, d: int) -> np.ndarray:
+    """|float32(any float64 evaluation of (-2 a.x + ||a||^2) + ||x||^2) - exact| <= 2^-24 |exact| + 1.01 (d + 4) 2^-52
+    (||a||^2 + ||x||^2): half a float32 ulp of the result plus the recursive-summation bound gamma_{d+3} of the three
+    float64 sums in any order, whose absolute terms add up to ||a||^2 + 2 |a|.|x| + ||x||^2 <= 2 (||a||^2 + ||x||^2)."""
+    A64 = np.asarray(A, f32).astype(np.float64)
+    X64 = np.asarray(X, f32).astype(np.float64)
+    mag = (A64 * A64).sum(axis=1)[:, None] + (X64 * X64).sum(axis=1)[None, :]
+    return 2.0 ** -24 * np.abs(sqdist_exact(A, X)) + 1.01 * (d + 4) * 2.0 ** -52 * mag
+
+
 def kmeans_plusplus(X: np.ndarray, k: int, rs: np.random.RandomState, w: np.ndarray | None = None):
     n = X.shape[0]
     w = np.ones(n, dtype=X.dtype) if w is None else w

@@ -8,6 +8,7 @@ import torch
 from oracle import kmeans_oracle as KO
 from oracle import mel_oracle as MO
 from oracle import models_oracle as OM
+from tests import kmeans_cases as KC
 from tests.golden import fixtures as FX
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -114,6 +115,48 @@ def test_estep_restatement_matches_blas(n, d, k):
         for s in range(0, n, KO.CHUNK):
             np.testing.assert_array_equal(KO.estep_dist(X[s:s + KO.CHUNK], C, cn),
                                           KO.estep_dist_blas(X[s:s + KO.CHUNK], C, cn))
+
+
+@pytest.mark.parametrize("d", [3, 37, 130])
+def test_sqdist_upcast_within_derived_bound_of_exact(d):
+    """oracle sqdist_exact / sqdist_bound (the yardstick of the float64 distance kernels): sklearn's
+    _euclidean_distances_upcast restatement stays inside the derived bound of the exact squared distance, on rows far
+    from the origin with an exact duplicate, a one-ulp neighbour and a 1e-4 relative neighbour among the candidates."""
+    X = KC.dup_rows(KC.SQDIST_N, d, seed=d)
+    A = X[KC.SQDIST_CAND]
+    exact = KO.sqdist_exact(A, X)
+    bound = KO.sqdist_bound(A, X, d)
+    assert exact.dtype == np.float64 and exact.shape == (len(KC.SQDIST_CAND), KC.SQDIST_N) and (exact >= 0).all()
+    assert exact[0, 0] == 0.0 and exact[0, 1] == 0.0 and 0.0 < exact[0, 2] < exact[0, 3] < 1e-3 * exact[0, 5]
+    # the exact value against an independent evaluation: the float64 sum of squared float64 differences is within
+    # (d + 3) 2^-53 relative of it (no cancellation between its non-negative terms)
+    direct = ((A.astype(np.float64)[:, None, :] - X.astype(np.float64)[None, :, :]) ** 2).sum(axis=2)
+    assert (np.abs(direct - exact) <= (d + 3) * 2.0 ** -53 * exact).all()
+    err = np.abs(KO._sqdist_upcast(A, X).astype(np.float64) - exact)
+    print(f"d={d}: worst err / bound {float((err / bound).max()):.3f}")
+    assert (err <= bound).all()
+
+
+@pytest.mark.parametrize("case", KC.FIT_CASES, ids=KC.FIT_IDS)
+def test_kmeans_oracle_matches_live_sklearn_off_workload_shapes(case):
+    """Every whole-fit input of tests/test_kmeans_ops_gpu.py (odd d, d < 32, k up to 55, n_init up to 20, an input
+    whose empty clusters are relocated): the oracle's KMeans equals live single-thread sklearn -- labels, inertia and
+    n_iter -- so the GPU tests may compare against the oracle alone."""
+    import warnings
+    from sklearn.cluster import KMeans as SK
+    from threadpoolctl import threadpool_info, threadpool_limits
+    archs = {i.get("architecture") for i in threadpool_info() if i.get("internal_api") == "openblas"}
+    if archs != {"SkylakeX"}:     # as test_estep_restatement_matches_blas: live sklearn's labels follow the host's sgemm
+        pytest.skip(f"the restatement is of the SkylakeX OpenBLAS kernels the fixtures were made with, not {archs}")
+    name, kind, n, d, true_k, k, n_init = case
+    X = KC.fit_input(case)
+    assert X.shape == (n, d) and X.dtype == np.float32
+    ours = KO.KMeans(k, random_state=42, n_init=n_init).fit(X)
+    with threadpool_limits(1), warnings.catch_warnings():
+        warnings.simplefilter("ignore")          # fewer distinct clusters than k on the repeated-row input
+        ref = SK(n_clusters=k, random_state=42, n_init=n_init).fit(X)
+    np.testing.assert_array_equal(ours.labels_, ref.labels_)
+    assert ours.inertia_ == ref.inertia_ and ours.n_iter_ == ref.n_iter_
 
 
 def test_scaler_oracle_matches_fixture():
