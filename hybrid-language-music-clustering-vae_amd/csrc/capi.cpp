@@ -1,4 +1,5 @@
 // extern "C" boundary of libhlmc (declared in include/hlmc.h).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -436,12 +437,12 @@ int hlmc_km_rowdist(void* stream, const float* X, int64_t n, int d, const float*
 int64_t hlmc_silhouette_workspace(int64_t n, int k) { return (int64_t)metrics::silhouette_workspace(n, k); }
 int hlmc_silhouette(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* samples,
                     double* score, void* ws, int64_t ws_bytes) {
-    return metrics::silhouette(S(stream), X, n, d, labels, k, samples, score, ws, (size_t)ws_bytes);
+    return metrics::silhouette(S(stream), X, n, d, labels, k, samples, score, ws, (size_t)std::max<int64_t>(0, ws_bytes));
 }
 int64_t hlmc_cluster_scores_workspace(int k, int d) { return (int64_t)metrics::cluster_scores_workspace(k, d); }
 int hlmc_cluster_scores(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* out2,
                         void* ws, int64_t ws_bytes) {
-    return metrics::cluster_scores(S(stream), X, n, d, labels, k, out2, ws, (size_t)ws_bytes);
+    return metrics::cluster_scores(S(stream), X, n, d, labels, k, out2, ws, (size_t)std::max<int64_t>(0, ws_bytes));
 }
 
 // ------------------------------------------------------------------------------------ DBSCAN

@@ -1144,6 +1144,7 @@ __global__ void clip_max_kernel(const float* __restrict__ S, int64_t per, unsign
 int power_to_db(hipStream_t s, const float* S, int64_t B, int64_t per, int ref_max, float ref_value, float amin,
                 float top_db, float* out, void* ws) {
     HLMC_CHECK_ARG(S && out && ws && B > 0 && B <= 65535, "bad power_to_db arguments");
+    HLMC_CHECK_ARG(per > 0 && per <= INT32_MAX, "bad power_to_db arguments: per_clip outside [1, 2^31)");
     unsigned* cmax = reinterpret_cast<unsigned*>(ws);
     unsigned* cmin = cmax + B;
     init_minmax_kernel<<<(unsigned)((B + 255) / 256), 256, 0, s>>>(cmax, cmin, B);
@@ -1327,7 +1328,7 @@ int colstats(hipStream_t s, const float* x, int64_t n, int64_t cols, const doubl
 
 int zscore(hipStream_t s, const float* x, int64_t n, int64_t cols, const double* mean, const double* scale, int dtype,
            void* out) {
-    HLMC_CHECK_ARG(x && mean && scale && out, "bad zscore arguments");
+    HLMC_CHECK_ARG(x && mean && scale && out && n > 0 && cols > 0, "bad zscore arguments");
     if (dtype == HLMC_BF16)
         zscore_kernel<bf16><<<gridn(n * cols), 256, 0, s>>>(x, n, cols, mean, scale, reinterpret_cast<bf16*>(out));
     else

@@ -255,6 +255,16 @@ def scaler_finalize(n_total, col_sum, corr, m2):
     return mean, var, scale
 
 
+def _check_n_features(X, fitted):
+    """sklearn's check_n_features (reset=False), on the shape alone: nothing is converted or moved to the device."""
+    shape = tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
+    if len(shape) < 2:
+        raise ValueError(f"Expected an array of at least 2 dimensions, got shape {shape}")
+    cols = int(np.prod(shape[1:], dtype=np.int64))
+    if cols != fitted:
+        raise ValueError(f"X has {cols} features, but StandardScaler is expecting {fitted} features as input.")
+
+
 class StandardScaler:
     """sklearn.preprocessing.StandardScaler (with_mean, with_std) with float64 accumulators on the GPU.
 
@@ -279,14 +289,15 @@ class StandardScaler:
         ws = torch.empty(max(16, int(L.lib().hlmc_colstats_workspace(n, cols))), dtype=torch.uint8, device=dev)
         total = self._allreduce(torch.tensor([float(n)], dtype=torch.float64, device=dev))
         s = torch.empty(cols, dtype=torch.float64, device=dev)
-        L.check(L.lib().hlmc_colstats_sum(L.stream(), x.data_ptr(), n, cols, s.data_ptr(), ws.data_ptr()))
+        L.check(L.lib().hlmc_colstats_sum(L.stream(), x.data_ptr(), n, cols, s.data_ptr(), ws.data_ptr()),
+                "hlmc_colstats_sum")
         self._allreduce(s)
         N = float(total.item())
         mean = s / N
         corr = torch.empty_like(s)
         m2 = torch.empty_like(s)
         L.check(L.lib().hlmc_colstats_centered(L.stream(), x.data_ptr(), n, cols, mean.data_ptr(), corr.data_ptr(),
-                                               m2.data_ptr(), ws.data_ptr()))
+                                               m2.data_ptr(), ws.data_ptr()), "hlmc_colstats_centered")
         self._allreduce(corr)
         self._allreduce(m2)
         mean, var, scale = scaler_finalize(N, s, corr, m2)
@@ -299,6 +310,7 @@ class StandardScaler:
         return self
 
     def transform(self, X, out_dtype=torch.float32):
+        _check_n_features(X, self.n_features_in_)   # first: the kernel indexes mean_ / scale_ by column unchecked
         was_np = not torch.is_tensor(X)
         x = X if torch.is_tensor(X) else torch.as_tensor(np.asarray(X, dtype=np.float32))
         shape = x.shape

@@ -301,13 +301,30 @@ int hlmc_km_inertia_batch(void* stream, const float* X, int64_t n, int d, const 
 /* ============================================================== cluster-quality metrics
  * sklearn.metrics.silhouette_score / silhouette_samples (metric "euclidean"), replacing the calls at
  * src/Convolutional_VAE.py:320,337,361,399, src/Conditional_VAE.py:298, src/Simple_VAE.py:247,256,262.
- * X [n][d] f32 (d <= 128), labels int32 in [0, k), 2 <= k <= 64.  samples (nullable) [n] f64, score: device
- * f64 scalar.  Deterministic (fixed-order f64 reductions). */
+ * X [n][d] f32 (n >= 2, 1 <= d <= 128), 2 <= k <= n - 1 (sklearn's range; k above the 64 -- 62 for d > 64 --
+ * accumulator rows LDS holds takes one distance launch per label window).  samples (nullable) [n] f64, score: device
+ * f64 scalar.  Deterministic (fixed-order f64 reductions).
+ * PRECONDITION (both entry points): labels are int32 in [0, k).  Sizes, pointers and the workspace size are checked on
+ * the host; label VALUES are not: the kernels index the counts, the centroids and LDS with them unchecked (the Python
+ * wrappers encode labels with np.unique, which guarantees it).
+ * Distances are float32 sums of squared direct differences (no Gram form), float32 sqrt, summed in float64.
+ * Workspace of hlmc_silhouette (bytes; r256 = round up to 256):
+ *   [0, 8 n k)                 S [n][k] f64, S[i][c] = sum over rows j with label c of ||x_i - x_j||
+ *   [r256(8 n k), + r256(4 k)) counts [k] int32 (rows per label)
+ *   then 512 f64               block partial sums of the coefficients */
 int64_t hlmc_silhouette_workspace(int64_t n, int k);
 int hlmc_silhouette(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* samples,
                     double* score, void* ws, int64_t ws_bytes);
 /* out2 (device f64[2]) = { davies_bouldin_score, calinski_harabasz_score } (src/Convolutional_VAE.py:400,
- * src/Simple_VAE.py:257,263); every label in [0, k) must occur. */
+ * src/Simple_VAE.py:257,263), sklearn 1.7 branches included (a centroid distance of 0 contributes 0; all intra
+ * distances or all centroid distances within 1e-8 of 0 -> Davies-Bouldin 0; zero intra dispersion -> Calinski-Harabasz
+ * 1).  n >= 2, 1 <= d <= 4096, 2 <= k <= min(n - 1, 1024); labels as above, and every label in [0, k) must occur.
+ * All accumulation in float64, fixed order.  Workspace (f64 units unless stated, in this order):
+ *   part [64][k][d]   per row block: sum of the block's rows of each label
+ *   part2 [64][k][2]  per row block: sum of ||x - cent|| and of ||x - cent||^2 of each label
+ *   cent [k][d]       centroids;   mean [d]  grand mean
+ *   counts [k] int32  padded to a multiple of 256 bytes
+ *   intra [k]         mean distance of a label's rows to its centroid */
 int64_t hlmc_cluster_scores_workspace(int k, int d);
 int hlmc_cluster_scores(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* out2,
                         void* ws, int64_t ws_bytes);

@@ -346,3 +346,129 @@ def test_loss_restatement_matches_torch_float64_autograd():
     sums0, _, drt0, _, _ = OO.loss_sums_and_grads(ra.detach().numpy(), a.numpy(), None, None, mu.detach().numpy(),
                                                   lv.detach().numpy(), coef)
     assert sums0[1] == 0.0 and drt0 is None and sums0[0] == sums[0] and sums0[2] == sums[2]
+
+
+# ---------------------------------------------------------------- metric / scaler op-level oracles and their bounds
+def _sil_all_inputs():
+    from tests import metrics_cases as MC
+    return [(c[0], *MC.sil_input(c)[:2]) for c in MC.SIL_CASES] + [(k, *v) for k, v in MC.sil_semantic_inputs().items()]
+
+
+def test_silhouette_float32_restatement_within_bounds_on_every_gpu_input():
+    """The kernel's arithmetic restated in numpy float32 (sequential sum, no fma) stays inside sums_bound /
+    samples_bound / score_bound on every input of tests/test_metrics_ops_gpu.py: a bound wrong as stated fails here,
+    without a GPU."""
+    from oracle import metrics_oracle as MT
+    worst = [0.0, 0.0, 0.0]
+    for name, X, y in _sil_all_inputs():
+        d = X.shape[1]
+        S, S32 = MT.silhouette_sums(X, y), MT.silhouette_sums_f32(X, y)
+        s, s32 = MT.silhouette_from_sums(S, y), MT.silhouette_from_sums(S32, y)
+        eS, es = np.abs(S32 - S), np.abs(s32 - s)
+        assert (eS <= MT.sums_bound(S, d)).all(), name
+        assert (es <= MT.samples_bound(s, d)).all(), name
+        assert abs(s32.mean() - s.mean()) <= MT.score_bound(s, d), name
+        with np.errstate(invalid="ignore", divide="ignore"):
+            worst[0] = max(worst[0], float(np.nanmax(eS / MT.sums_bound(S, d))))
+        worst[1] = max(worst[1], float((es / MT.samples_bound(s, d)).max()))
+        worst[2] = max(worst[2], abs(s32.mean() - s.mean()) / MT.score_bound(s, d))
+    print("worst err / bound of the float32 restatement: S %.3f, samples %.3f, score %.3f" % tuple(worst))
+    assert worst[0] > 0.01, "sums_bound is too slack to catch anything"
+
+
+def test_silhouette_oracle_semantics_match_live_sklearn():
+    from sklearn.metrics import silhouette_samples as sk_samples
+    from oracle import metrics_oracle as MT
+    from tests import metrics_cases as MC
+    for name, (X, y) in MC.sil_semantic_inputs().items():
+        ref = sk_samples(X, y)
+        got = MT.silhouette_samples(X, y)
+        np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-6, err_msg=name)
+    X, y = MC.sil_semantic_inputs()["singleton"]
+    assert MT.silhouette_samples(X, y)[17] == 0.0
+    X, y = MC.sil_semantic_inputs()["duplicates"]
+    assert (MT.silhouette_samples(X, y)[y == 0] == 1.0).all()
+    X, y = MC.sil_semantic_inputs()["identical_rows_in_two_clusters"]
+    assert (MT.silhouette_samples(X, y)[y < 2] == 0.0).all()
+
+
+def test_cluster_stats_oracle_bounds_contain_a_float64_evaluation_and_match_sklearn():
+    """oracle cluster_stats (longdouble) against the plain float64 numpy evaluation within its own derived bounds on
+    every input of the GPU test, and its sklearn branches against live sklearn on the degenerate sets."""
+    from sklearn.metrics import calinski_harabasz_score, davies_bouldin_score
+    from oracle import metrics_oracle as MT
+    from tests import metrics_cases as MC
+    worst = [0.0, 0.0]
+    for case in MC.CLU_CASES:
+        X, y, k = MC.clu_input(case)
+        st = MT.cluster_stats(X, y)
+        assert (st["counts"] == np.bincount(y, minlength=k)).all() and (st["counts"] > 0).all(), case[0]
+        X64 = X.astype(np.float64)
+        cent = np.stack([X64[y == c].mean(0) for c in range(k)])
+        assert (np.abs(cent - st["cent"]) <= st["cent_bound"]).all(), case[0]
+        intra = np.array([np.sqrt(((X64[y == c] - cent[c]) ** 2).sum(1)).mean() for c in range(k)])
+        assert (np.abs(intra - st["intra"]) <= st["intra_bound"]).all(), case[0]
+        db, ch = MT.davies_bouldin_score(X, y), MT.calinski_harabasz_score(X, y)
+        assert abs(db - st["db"]) <= st["db_bound"], (case[0], db, st["db"], st["db_bound"])
+        assert abs(ch - st["ch"]) <= st["ch_bound"], (case[0], ch, st["ch"], st["ch_bound"])
+        assert st["db_bound"] <= 1e-9 * st["db"] and st["ch_bound"] <= 1e-9 * st["ch"], case[0]
+        worst = [max(worst[0], abs(db - st["db"]) / st["db_bound"]), max(worst[1], abs(ch - st["ch"]) / st["ch_bound"])]
+    print("worst err / bound of numpy float64: DB %.4f, CH %.4f" % tuple(worst))
+    for name, (X, y, db, ch) in MC.DEGENERATE.items():
+        X = np.asarray(X, dtype=np.float32)
+        st = MT.cluster_stats(X, y)
+        assert st["db"] == pytest.approx(db, abs=1e-15) and st["ch"] == pytest.approx(ch, abs=1e-15), name
+        assert davies_bouldin_score(X, y) == pytest.approx(db, abs=1e-7), name
+        assert calinski_harabasz_score(X, y) == pytest.approx(ch, abs=1e-7), name
+
+
+def test_scaler_oracle_matches_live_sklearn_and_its_bounds_contain_float64_numpy():
+    from sklearn.preprocessing import StandardScaler as SK
+    from oracle import scaler_oracle as SO
+    from tests import scaler_cases as SC
+    for n, cols in SC.COLSTATS_CASES:
+        X = SC.colstats_input(n, cols)
+        sk = SK().fit(X)
+        mean, var, scale = SO.scaler_fit(X)
+        np.testing.assert_allclose(mean, sk.mean_, rtol=1e-14, err_msg=str((n, cols)))
+        np.testing.assert_allclose(var, sk.var_, rtol=1e-10, err_msg=str((n, cols)))
+        np.testing.assert_allclose(scale, sk.scale_, rtol=1e-10, err_msg=str((n, cols)))
+        if cols > SC.SHIFTED_COL:
+            assert scale[SC.CONST_COL] == 1.0 and (n == 1 or abs(scale[SC.SHIFTED_COL] - 1e-2) < 5e-3)
+        np.testing.assert_array_equal(SO.zscore(X, sk.mean_, sk.scale_), sk.transform(X))
+        # numpy's float64 sums (pairwise, another order than the kernel's chunks) are inside the exact-sum bounds
+        X64 = X.astype(np.float64)
+        s, sb = SO.col_sums(X)
+        assert (np.abs(X64.sum(0) - s) <= sb).all()
+        m = s / n
+        corr, cb, m2, mb = SO.col_centered(X, m)
+        t = X64 - m
+        assert (np.abs(t.sum(0) - corr) <= cb).all() and (np.abs((t * t).sum(0) - m2) <= mb).all()
+
+
+def test_pool_and_db_restatements_within_bounds_on_every_gpu_input():
+    from oracle import scaler_oracle as SO
+    from tests import scaler_cases as SC
+    for kind in SC.POOL_KINDS:
+        for rows in SC.POOL_ROWS:
+            for cols in SC.POOL_COLS:
+                x = SC.pool_input(rows, cols, kind)
+                m, mb, sd, sb = SO.row_mean_std(x)
+                gm, gs = SO.row_mean_std_f64(x)
+                assert (np.abs(gm - m) <= mb).all() and (np.abs(gs - sd) <= sb).all(), (kind, rows, cols)
+                np.testing.assert_allclose(np.concatenate([gm, gs]), MO.mean_std_pool(x), rtol=1e-5, atol=1e-5)
+    worst = 0.0
+    for name, B, F, T, zero_clip, ref_max, top_db in SC.DB_CASES:
+        S = SC.db_input(B, F, T, seed=B + F + T, zero_clip=zero_clip).reshape(B, -1)
+        ref, bound, clamped = SO.power_to_db(S, ref_max=ref_max, top_db=top_db)
+        got = SO.power_to_db_f32(S, ref_max=ref_max, top_db=top_db)
+        err = np.abs(got - ref)
+        assert (err <= bound).all(), (name, float((err / bound).max()))
+        worst = max(worst, float((err[bound > 0] / bound[bound > 0]).max()))
+        if top_db is not None:
+            assert clamped.any(), name
+            for b in range(B):
+                assert (got[b][clamped[b]] == got[b].max() - np.float32(top_db)).all(), name
+        lib = np.stack([MO.power_to_db(s, ref=np.max if ref_max else 1.0, top_db=top_db) for s in S])
+        np.testing.assert_allclose(got, lib, atol=1e-4)
+    print("worst err / bound of the float32 dB restatement: %.3f" % worst)
