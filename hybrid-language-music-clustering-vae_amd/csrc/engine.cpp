@@ -21,6 +21,132 @@ constexpr int DEC_CH[7] = {512, 512, 256, 128, 64, 32, 1};
 
 inline int pad8(int64_t n) { return (int)((n + 7) & ~int64_t(7)); }
 
+// ============================================================================ weight-gradient queue
+// Weight and bias gradients have no consumer before Adam.  backward() hands them to this queue, which runs them on
+// a second stream (own split-K scratch) behind a fork: an event recorded on the caller's stream s after the data
+// gradient they read is written.  The critical path stays dgrad -> BN-backward -> dgrad on s and the wgrad GEMMs /
+// reduces fill the CUs it leaves idle.  A fork costs s a ~6 us bubble (measured: scripts/step_gaps.py), so items
+// wait here and are issued in batches behind one fork.  Every buffer an item reads is written once per backward, so
+// issuing it later is safe; it only waits longer.  backward() joins the stream before returning (or leaves the
+// join to adam_step: NetBase::overlap_adam).
+// HLMC_SIDE_STREAM=0 (on = false) runs every item at once on the caller's stream (A/B measurement aid).
+struct WgradQueue {
+    using Fn = std::function<int(hipStream_t, Ws)>;  // an item: its launches on the given stream and scratch
+    bool on = true;
+    Ws ws_main{nullptr, 0};  // scratch of the caller's stream (items run there when !on)
+    Ws ws_own{nullptr, 0};   // scratch of the second stream
+
+    WgradQueue() = default;
+    WgradQueue(const WgradQueue&) = delete;
+    ~WgradQueue() {
+        if (s2) (void)hipStreamDestroy(s2);
+        for (auto e : evs) (void)hipEventDestroy(e);
+        if (prelate_ev) (void)hipEventDestroy(prelate_ev);
+    }
+    // start of every backward: reads HLMC_SIDE_STREAM (once per process), creates the stream and its events
+    int init() {
+        static const bool env_off = [] {
+            const char* e = std::getenv("HLMC_SIDE_STREAM");
+            return e && e[0] == '0';
+        }();
+        on = !env_off;
+        if (on && !s2) {
+            // (default priority: the lowest priority removed the main queue's resource waits in the profile,
+            // 322 -> 108 us per step, but the step was 0.4% slower, 3 alternating rounds)
+            HLMC_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+            evs.resize(32);
+            // Both streams run on this device: the kernels' own device-scope release / acquire order every
+            // cross-stream hand-off, and the system-scope fence HIP adds to an event by default (host visibility,
+            // which no fork needs) is what made every fork a main-stream bubble.  Measured (3 alternating rounds):
+            // hipEventDisableSystemFence 126.7k vs 125.1k clips/s with HIP's default and 125.0k with
+            // hipEventReleaseToDevice
+            const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
+            for (auto& e : evs) HLMC_HIP(hipEventCreateWithFlags(&e, fl));
+            HLMC_HIP(hipEventCreateWithFlags(&prelate_ev, fl));
+        }
+        return HLMC_OK;
+    }
+    // Queue f behind the work issued so far on s.  Once `batch` items wait: fork, then main_work() -- the caller's
+    // next launches on s, ahead of the items' so the critical path does not wait for the host to issue them -- then
+    // the items.
+    template <class MainFn>
+    int queue(hipStream_t s, Fn f, int batch, MainFn main_work) {
+        if (!on) {
+            HLMC_TRY(main_work());
+            return f(s, ws_main);
+        }
+        q.push_back(std::move(f));
+        const bool go = (int)q.size() >= batch;
+        if (go) HLMC_TRY(fork(s));
+        HLMC_TRY(main_work());
+        return go ? issue() : (int)HLMC_OK;
+    }
+    int queue(hipStream_t s, Fn f, int batch) {
+        return queue(s, std::move(f), batch, [] { return (int)HLMC_OK; });
+    }
+    // run f now, behind a fork of its own (with everything queued before it)
+    int run(hipStream_t s, Fn f) { return queue(s, std::move(f), 1); }
+    // issue what waits (nothing queued: no fork)
+    int flush(hipStream_t s) {
+        if (q.empty()) return HLMC_OK;
+        HLMC_TRY(fork(s));
+        return issue();
+    }
+    // s continues after everything handed to the queue
+    int join(hipStream_t s) {
+        if (!on || !s2) return HLMC_OK;
+        HLMC_TRY(flush(s));
+        hipEvent_t e = next_ev();
+        HLMC_HIP(hipEventRecord(e, s2));
+        HLMC_HIP(hipStreamWaitEvent(s, e, 0));
+        return HLMC_OK;
+    }
+    // the pre-late point: every gradient handed over so far is final once the second stream passes it
+    int record_prelate(hipStream_t s) {
+        HLMC_TRY(flush(s));
+        HLMC_TRY(fork(s));
+        HLMC_HIP(hipEventRecord(prelate_ev, s2));
+        return HLMC_OK;
+    }
+    int wait_prelate(hipStream_t s) {
+        HLMC_HIP(hipStreamWaitEvent(s, prelate_ev, 0));
+        return HLMC_OK;
+    }
+    // ev: both streams passed this point
+    int record_bucket(hipStream_t s, hipEvent_t ev) {
+        HLMC_TRY(fork(s));
+        HLMC_TRY(issue());
+        HLMC_HIP(hipEventRecord(ev, s2));
+        return HLMC_OK;
+    }
+
+  private:
+    hipStream_t s2 = nullptr;
+    std::vector<hipEvent_t> evs;  // fork / join events, used round-robin
+    int ev_next = 0;
+    hipEvent_t prelate_ev = nullptr;
+    std::vector<Fn> q;
+    hipEvent_t next_ev() {
+        hipEvent_t e = evs[ev_next];
+        ev_next = (ev_next + 1) % (int)evs.size();
+        return e;
+    }
+    // the second stream continues after everything issued so far on s
+    int fork(hipStream_t s) {
+        hipEvent_t e = next_ev();
+        HLMC_HIP(hipEventRecord(e, s));
+        HLMC_HIP(hipStreamWaitEvent(s2, e, 0));
+        return HLMC_OK;
+    }
+    int issue() {
+        int rc = HLMC_OK;
+        for (auto& f : q)
+            if (rc == HLMC_OK) rc = f(s2, ws_own);
+        q.clear();
+        return rc;
+    }
+};
+
 template <typename T>
 class NetT : public NetBase {
   public:
@@ -127,11 +253,11 @@ class NetT : public NetBase {
         }
         const auto* jd = reinterpret_cast<const ops::AdamJob*>(state + ajobs_off);
         if (join_pending) {
-            // every gradient but the late ones is final once the side stream passed prelate_ev
+            // every gradient but the late ones is final once the weight-gradient stream passed the pre-late point
             const int tsplit = ajobs[this->late_params].tile0;
-            HLMC_HIP(hipStreamWaitEvent(s, prelate_ev, 0));
+            HLMC_TRY(wq.wait_prelate(s));
             HLMC_TRY(ops::adam_pack<T>(s, jd, (int)np, adam_tiles, a, coef_dev, tsplit));
-            HLMC_TRY(join(s));
+            HLMC_TRY(wq.join(s));
             join_pending = false;
             HLMC_TRY(ops::adam_pack<T>(s, jd, (int)np, tsplit, a, coef_dev, 0));
         } else {
@@ -147,8 +273,7 @@ class NetT : public NetBase {
 
     // ---------------------------------------------------------------- workspace
     char* ws = nullptr;
-    Ws scratch{nullptr, 0};
-    Ws scratch2{nullptr, 0};  // split-K / reduction scratch of the weight-gradient stream
+    Ws scratch{nullptr, 0};  // split-K / reduction scratch of the caller's stream (the weight-gradient stream's: wq)
     size_t scratch_off = 0, scratch2_off = 0, scratch_bytes = 0;
     int64_t planned_B = -1;
     size_t ws_total = 0;
@@ -193,144 +318,71 @@ class NetT : public NetBase {
     void set_ws(void* w) {
         ws = reinterpret_cast<char*>(w);
         scratch = Ws{reinterpret_cast<float*>(ws + scratch_off), scratch_bytes + 256};
-        scratch2 = Ws{reinterpret_cast<float*>(ws + scratch2_off), scratch_bytes + 256};
+        wq.ws_main = scratch;
+        wq.ws_own = Ws{reinterpret_cast<float*>(ws + scratch2_off), scratch_bytes + 256};
     }
 
-    // ---------------------------------------------------------------- weight-gradient stream
-    // Weight and bias gradients have no consumer before Adam.  backward() forks them onto a second stream
-    // (own split-K scratch) right after the data gradient they read is written, so the critical path stays
-    // dgrad -> BN-backward -> dgrad and the wgrad GEMMs / reduces fill the CUs it leaves idle.  Every buffer
-    // a forked op reads is written once per backward; backward() joins the stream before returning.
-    // HLMC_SIDE_STREAM=0 keeps everything on the caller's stream (A/B measurement aid).
-    hipStream_t s2 = nullptr;
-    std::vector<hipEvent_t> evs;
-    int ev_next = 0;
-    bool use_side = true;
-    hipEvent_t prelate_ev = nullptr;  // side stream passed every weight gradient except the late ones
-    bool join_pending = false;         // backward left the side stream running (NetBase::overlap_adam)
+    // ---------------------------------------------------------------- weight-gradient queue (policy)
+    WgradQueue wq;
+    bool join_pending = false;  // backward left the weight-gradient stream running (NetBase::overlap_adam)
     ~NetT() override {
-        if (s2) (void)hipStreamDestroy(s2);
-        for (auto e : evs) (void)hipEventDestroy(e);
         for (auto e : this->bucket_ev) (void)hipEventDestroy(e);
-        if (prelate_ev) (void)hipEventDestroy(prelate_ev);
     }
-    bool tail_overlap() const { return use_side && this->overlap_adam && !this->bucket_sync && this->late_params > 0; }
+    // conv layers / dense layers per fork.  Measured on the bench step (3 alternating rounds): conv 1 / dense 1
+    // 108.4k, 2 / 1 109.7k, 2 / 2 110.3k, 3 / 1 108.2k, 6 / 1 104.3k (the weight-gradient stream starts too late),
+    // 2 / 9 108.1k
+    static constexpr int side_batch() { return 2; }
+    static constexpr int dense_batch() { return 2; }
+    bool tail_overlap() const { return wq.on && this->overlap_adam && !this->bucket_sync && this->late_params > 0; }
     // called in backward once every non-late weight gradient has been issued
-    int prelate(hipStream_t s) {
-        if (!tail_overlap()) return HLMC_OK;
-        HLMC_TRY(flush_side(s));
-        HLMC_TRY(fork(s));
-        HLMC_HIP(hipEventRecord(prelate_ev, s2));
-        return HLMC_OK;
-    }
-    // end of backward: join the weight-gradient stream, or leave it to adam_step (tail overlap)
+    int prelate(hipStream_t s) { return tail_overlap() ? wq.record_prelate(s) : (int)HLMC_OK; }
     // a pending tail (backward without the adam_step that joins it) is joined before anything else runs
     int settle(hipStream_t s) override {
         if (!join_pending) return HLMC_OK;
         join_pending = false;
-        return join(s);
+        return wq.join(s);
     }
+    // end of backward: join the weight-gradient stream, or leave it to adam_step (tail overlap)
     int finish_backward(hipStream_t s) {
         if (tail_overlap()) {
             join_pending = true;
             return HLMC_OK;
         }
-        return join(s);
+        return wq.join(s);
     }
-    int side_init() {
-        static const bool env_off = [] {
-            const char* e = std::getenv("HLMC_SIDE_STREAM");
-            return e && e[0] == '0';
-        }();
-        use_side = !env_off;
-        if (use_side && !s2) {
-            // (default priority: the lowest priority removed the main queue's resource waits in the profile,
-            // 322 -> 108 us per step, but the step was 0.4% slower, 3 alternating rounds)
-            HLMC_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-            evs.resize(32);
-            const unsigned fl = hipEventDisableTiming | fork_event_scope();
-            for (auto& e : evs) HLMC_HIP(hipEventCreateWithFlags(&e, fl));
-            HLMC_HIP(hipEventCreateWithFlags(&prelate_ev, fl));
-        }
+    // bucket k of the data-parallel all-reduce is final once both streams pass this point
+    int mark(hipStream_t s, int k) {
+        if (!this->bucket_sync) return HLMC_OK;
+        HLMC_CHECK_ARG(k >= 0 && k < (int)this->bucket_ev.size(), "bucket index");
+        if (wq.on && k + 1 < (int)this->bucket_ev.size()) return wq.record_bucket(s, this->bucket_ev[k]);
+        // the last bucket: the caller has joined the weight-gradient stream
+        HLMC_HIP(hipEventRecord(this->bucket_ev[k], s));
+        return HLMC_OK;
+    }
+
+    // ---------------------------------------------------------------- step prologues
+    int begin_forward(hipStream_t s, const ForwardArgs& a) {
+        HLMC_CHECK_ARG(a.B >= 2 || !a.train, "BatchNorm in train mode needs batch >= 2");
+        ws_bytes((int)a.B);
+        set_ws(a.ws);
+        HLMC_TRY(settle(s));
+        HLMC_TRY(pack_all(s));
+        if (a.train) HLMC_TRY(zero_acc_fwd(s));
+        this->last_full_forward = !a.encode_only && !a.decode_only;
+        return HLMC_OK;
+    }
+    int begin_backward(hipStream_t s, const BackwardArgs& a) {
+        HLMC_CHECK_ARG((int)a.B == planned_B, "backward batch differs from the last forward");
+        HLMC_CHECK_ARG(this->last_full_forward, "backward needs a full hlmc_net_forward (not encode / decode)");
+        set_ws(a.ws);
+        HLMC_TRY(wq.init());
         if (this->bucket_sync && this->bucket_ev.size() != this->bucket_starts.size()) {
             for (auto e : this->bucket_ev) (void)hipEventDestroy(e);
             this->bucket_ev.assign(this->bucket_starts.size(), nullptr);
             for (auto& e : this->bucket_ev) HLMC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
-        return HLMC_OK;
-    }
-    // fence of the fork / join events.  Both streams run on this device: the kernels' own device-scope
-    // release / acquire order every cross-stream hand-off, and the system-scope fence HIP adds to an event by
-    // default (host visibility, which no fork needs) is what made every fork a main-stream bubble.  Measured (3
-    // alternating rounds): hipEventDisableSystemFence 126.7k vs 125.1k clips/s with HIP's default and 125.0k with
-    // hipEventReleaseToDevice
-    static unsigned fork_event_scope() { return (unsigned)hipEventDisableSystemFence; }
-    hipEvent_t next_ev() {
-        hipEvent_t e = evs[ev_next];
-        ev_next = (ev_next + 1) % (int)evs.size();
-        return e;
-    }
-    // the weight-gradient stream continues after everything issued so far on s
-    int fork(hipStream_t s) {
-        hipEvent_t e = next_ev();
-        HLMC_HIP(hipEventRecord(e, s));
-        HLMC_HIP(hipStreamWaitEvent(s2, e, 0));
-        return HLMC_OK;
-    }
-    int join(hipStream_t s) {
-        if (!use_side || !s2) return HLMC_OK;
-        HLMC_TRY(flush_side(s));
-        hipEvent_t e = next_ev();
-        HLMC_HIP(hipEventRecord(e, s2));
-        HLMC_HIP(hipStreamWaitEvent(s, e, 0));
-        return HLMC_OK;
-    }
-    // Weight-gradient work queued for the second stream.  A fork (event record on s, wait on s2) costs the main
-    // stream a ~6 us bubble (measured: scripts/step_gaps.py), so queued work is issued in batches behind one
-    // fork: the queue is flushed once it holds `batch` items (and by join / mark / prelate).  Every buffer a
-    // queued op reads is written once per backward, so issuing it later is safe; it only waits longer.
-    using SideFn = std::function<int(hipStream_t, Ws)>;
-    std::vector<SideFn> side_q;
-    int issue_side() {
-        int rc = HLMC_OK;
-        for (auto& f : side_q)
-            if (rc == HLMC_OK) rc = f(s2, scratch2);
-        side_q.clear();
-        return rc;
-    }
-    int flush_side(hipStream_t s) {
-        if (side_q.empty()) return HLMC_OK;
-        HLMC_TRY(fork(s));
-        return issue_side();
-    }
-    // queue f(stream, scratch) for the weight-gradient stream (ordered after the work issued so far on s);
-    // inline on s without the second stream
-    int defer_side(hipStream_t s, SideFn f, int batch) {
-        if (!use_side) return f(s, scratch);
-        side_q.push_back(std::move(f));
-        return (int)side_q.size() >= batch ? flush_side(s) : HLMC_OK;
-    }
-    // conv layers / dense layers per fork.  Measured on the bench step (scripts/gpu_r3_knobs.sh, 3 alternating
-    // rounds): conv 1 / dense 1 108.4k, 2 / 1 109.7k, 2 / 2 110.3k, 3 / 1 108.2k, 6 / 1 104.3k (the weight-gradient
-    // stream starts too late), 2 / 9 108.1k
-    static constexpr int side_batch() { return 2; }
-    static constexpr int dense_batch() { return 2; }
-    // run f on the weight-gradient stream now (with everything queued before it)
-    int side(hipStream_t s, SideFn f) { return defer_side(s, std::move(f), 1); }
-    // weight gradients of the dense layers: on the second stream (measured round 1: 93.3k vs 86.5k clips/s inline)
-    bool dense_side_on() const { return use_side; }
-    // bucket k of the data-parallel all-reduce is final once both streams pass this point
-    int mark(hipStream_t s, int k) {
-        if (!this->bucket_sync) return HLMC_OK;
-        HLMC_CHECK_ARG(k >= 0 && k < (int)this->bucket_ev.size(), "bucket index");
-        if (use_side && k + 1 < (int)this->bucket_ev.size()) {
-            if (side_q.empty()) HLMC_TRY(fork(s));
-            else HLMC_TRY(flush_side(s));
-            HLMC_HIP(hipEventRecord(this->bucket_ev[k], s2));
-        } else {  // the last bucket: the caller has joined the weight-gradient stream
-            HLMC_HIP(hipEventRecord(this->bucket_ev[k], s));
-        }
-        return HLMC_OK;
+        HLMC_TRY(settle(s));
+        return zero_acc_bwd(s);
     }
 
     // ---------------------------------------------------------------- reparameterisation
@@ -341,9 +393,13 @@ class NetT : public NetBase {
     int reparam(hipStream_t s, const float* eps_in, const float* mu, const float* lv, float* eps_keep, int B, int L,
                 T* z, int ldz, float* mu_out, float* lv_out) {
         if (eps_in) return ops::reparam_fwd<T>(s, mu, lv, eps_in, B, L, z, ldz, mu_out, lv_out, eps_keep);
+        return ops::reparam_rng<T>(s, mu, lv, this->rng_seed, take_rng(B, L), B, L, eps_keep, z, ldz, mu_out, lv_out);
+    }
+    // the Philox offset of a forward's B x L noise values; the stream advances past them (kept a multiple of 4)
+    uint64_t take_rng(int B, int L) {
         const uint64_t off = this->rng_offset;
         this->rng_offset += ((uint64_t)B * L + 3) & ~uint64_t(3);
-        return ops::reparam_rng<T>(s, mu, lv, this->rng_seed, off, B, L, eps_keep, z, ldz, mu_out, lv_out);
+        return off;
     }
     // encode only: the latent outputs
     int latent_out(hipStream_t s, const ForwardArgs& a, const float* mu, const float* lv, int64_t nl) {
@@ -361,11 +417,7 @@ class NetT : public NetBase {
         if (a.encode_only)
             return ops::heads_reparam<T>(s, scratch.p, S, B, L, P[mu_b], P[lv_b], mu, lv, a.mu, a.logvar, nullptr, 0, 0,
                                          nullptr, nullptr, 0);
-        uint64_t off = 0;
-        if (!a.eps) {
-            off = this->rng_offset;
-            this->rng_offset += ((uint64_t)B * L + 3) & ~uint64_t(3);
-        }
+        const uint64_t off = a.eps ? 0 : take_rng(B, L);
         return ops::heads_reparam<T>(s, scratch.p, S, B, L, P[mu_b], P[lv_b], mu, lv, a.mu, a.logvar, a.eps,
                                      this->rng_seed, off, eps_keep, z, ldz);
     }
@@ -408,18 +460,11 @@ class NetT : public NetBase {
                 return ops::linear<T, T>(s, dy, lddy, B, N, p1, ldw, nullptr, K, dx, lddx, 0, acc, scratch, relu_ref, no);
             });
     }
-    // wg: the layer's weight-gradient launch (weight-gradient stream), dxf: its data-gradient launches (on s)
+    // wg: the layer's weight-gradient launch (weight-gradient stream: measured round 1, 93.3k vs 86.5k clips/s
+    // inline), dxf: its data-gradient launches (on s, between the fork and the queued launches)
     template <class DxFn>
-    int dense_bwd(hipStream_t s, SideFn wg, DxFn dxf) {
-        if (!dense_side_on()) {
-            HLMC_TRY(dxf());
-            return wg(s, scratch);
-        }
-        side_q.push_back(std::move(wg));
-        const bool go = (int)side_q.size() >= dense_batch();
-        if (go) HLMC_TRY(fork(s));
-        HLMC_TRY(dxf());
-        return go ? issue_side() : HLMC_OK;
+    int dense_bwd(hipStream_t s, WgradQueue::Fn wg, DxFn dxf) {
+        return wq.queue(s, std::move(wg), dense_batch(), dxf);
     }
     // The latent heads' backward from gml = [gmu | glv] ([B][ldg], 2L columns): both layers' weight and bias gradients
     // as one launch.  The data gradient stays two GEMMs over the column halves, the second accumulating (relu_ref / no
@@ -499,47 +544,25 @@ class NetT : public NetBase {
         HLMC_TRY(ops::bn_eval_stats(s, RM[bn], RV[bn], C, kBnEps, mean, inv));
         return ops::bn_act<T>(s, y, R, C, mean, inv, P[g], P[beta], act, mask, mscale, a, lda, fo, hw);
     }
-    // fused: moments delivered by the kernel that wrote da (nullable); bias_side: the conv bias column sums are
-    // reduced into the gradient on the weight-gradient stream (else here)
-    // defer_bias: leave the bias reduction to the next side_bias() call (one fork for it and the layer's weight
-    // gradient: every fork puts an event marker on the main stream, measured as a ~10 us bubble)
-    int bn_bwd(hipStream_t s, const T* da, int lda, const T* y, int64_t R, int C, const BnBufs& bb, int g, int beta,
-               int act, const uint8_t* mask, float mscale, T* dy, int bias, const ops::BnBwdFuse* fused = nullptr,
-               bool bias_side = false, bool defer_bias = false) {
-        const bool on_side = bias >= 0 && use_side && bias_side;
-        const XAcc bacc = bias >= 0 ? acc_bias(bb) : XAcc{};
-        HLMC_TRY(ops::bn_act_bwd<T>(s, da, lda, y, R, C, AF(bb.mean), AF(bb.inv), P[g], P[beta], act, mask, mscale, dy,
-                                    G[g], G[beta], acc_mom(bb), fused, bacc,
-                                    (bias >= 0 && !on_side) ? G[bias] : nullptr, AF(bb.sums)));
-        if (on_side) {
-            float* gb = G[bias];
-            if (defer_bias)
-                pend_bias = PendingBias{bacc, C, gb};
-            else
-                HLMC_TRY(side(s, [=](hipStream_t q, Ws) { return ops::colsum_finalize(q, bacc, C, gb); }));
-        }
-        return HLMC_OK;
-    }
+    // bias column sums that bn_bwd accumulated and left to the caller: gb = the finalized sums of acc (gb null: none)
     struct PendingBias {
         XAcc acc;
         int C = 0;
         float* gb = nullptr;
     };
-    PendingBias pend_bias;
-    PendingBias take_bias() {
-        const PendingBias pb = pend_bias;
-        pend_bias = PendingBias{};
-        return pb;
-    }
-    // f on the weight-gradient stream, after the bias reduction a preceding bn_bwd(defer_bias) left pending
-    // (queued: flushed every side_batch() layers)
-    int side_bias(hipStream_t s, SideFn f) {
-        const PendingBias pb = pend_bias;
-        pend_bias = PendingBias{};
-        return defer_side(s, [pb, f](hipStream_t q, Ws sc) {
-            if (pb.gb) HLMC_TRY(ops::colsum_finalize(q, pb.acc, pb.C, pb.gb));
-            return f(q, sc);
-        }, side_batch());
+    // fused: moments delivered by the kernel that wrote da (nullable)
+    // to_wgrad (nullable): with the weight-gradient stream on, the bias gradient is not written here; *to_wgrad
+    // describes it and the caller hands it to the layer's weight gradient, whose reduce launch writes it (no launch
+    // and no fork of its own).  Otherwise G[bias] is written here and *to_wgrad is empty.
+    int bn_bwd(hipStream_t s, const T* da, int lda, const T* y, int64_t R, int C, const BnBufs& bb, int g, int beta,
+               int act, const uint8_t* mask, float mscale, T* dy, int bias, const ops::BnBwdFuse* fused = nullptr,
+               PendingBias* to_wgrad = nullptr) {
+        const bool hand_off = bias >= 0 && wq.on && to_wgrad;
+        const XAcc bacc = bias >= 0 ? acc_bias(bb) : XAcc{};
+        if (to_wgrad) *to_wgrad = hand_off ? PendingBias{bacc, C, G[bias]} : PendingBias{};
+        return ops::bn_act_bwd<T>(s, da, lda, y, R, C, AF(bb.mean), AF(bb.inv), P[g], P[beta], act, mask, mscale, dy,
+                                  G[g], G[beta], acc_mom(bb), fused, bacc,
+                                  (bias >= 0 && !hand_off) ? G[bias] : nullptr, AF(bb.sums));
     }
     ops::BnBwdFuse fuse4{};  // the decoder's last BN layer: moments from the output convT's data gradient
 
@@ -547,6 +570,8 @@ class NetT : public NetBase {
     struct Enc {
         int w[6], b[6], g[6], beta[6], bn[6];
         int H = 0, W = 0;
+        int rows(int l) const { return H >> l; }  // layer l's input grid (layer l - 1's output): halved per layer
+        int cols(int l) const { return W >> l; }
         size_t y[6], a[6], dy[6];  // dy: grad wrt the conv output (read by the forked wgrad); a[5]: see enc_fwd
         // the caller's input of the last full forward: the first conv's weight gradient reads it in backward (the
         // ABI contract keeps in0 alive and unchanged until then: hlmc.h hlmc_net_forward)
@@ -566,26 +591,24 @@ class NetT : public NetBase {
         }
     }
     void enc_plan(Arena& A, int64_t B) {
-        int h = enc.H, w = enc.W;
         for (int l = 0; l < 6; ++l) {
             const int ci = ENC_CH[l], co = ENC_CH[l + 1];
+            const int h = enc.rows(l), w = enc.cols(l), ho = enc.rows(l + 1), wo = enc.cols(l + 1);
             if (l > 0) {
                 need(ops::conv_s2_ws<T>((int)B, h, w, ci, co));
-                need(ops::subpixel_ws<T>((int)B, h / 2, w / 2, co, ci));
-                need(ops::wgrad_s2_ws<T>((int)B, h / 2, w / 2, co, ci));
+                need(ops::subpixel_ws<T>((int)B, ho, wo, co, ci));
+                need(ops::wgrad_s2_ws<T>((int)B, ho, wo, co, ci));
             } else {
-                need(ops::wgrad_c1_ws((int)B, h / 2, w / 2, co));
+                need(ops::wgrad_c1_ws((int)B, ho, wo, co));
             }
-            h /= 2;
-            w /= 2;
-            const size_t n = (size_t)B * h * w * co;
+            const size_t n = (size_t)B * ho * wo * co;
             enc.y[l] = A.take(n * sizeof(T));
             enc.a[l] = l < 5 ? A.take(n * sizeof(T)) : 0;
             enc.dy[l] = A.take(n * sizeof(T));
             enc.bb[l] = bn_plan(A, co);
         }
     }
-    size_t enc_max_elems(int64_t B) const { return (size_t)B * (enc.H / 2) * (enc.W / 2) * 32; }
+    size_t enc_max_elems(int64_t B) const { return (size_t)B * enc.rows(1) * enc.cols(1) * 32; }
     // train-mode BatchNorm + LeakyReLU of layer l's output applied by the next conv while it stages its input
     // (ops::BnInput: the LDS halo-tile kernels) instead of a bn_act pass; the activation is written by that kernel
     ops::BnInput bn_input(const BnBufs& bb, int bn, int g, int beta, int64_t R, size_t a_off) {
@@ -595,7 +618,6 @@ class NetT : public NetBase {
     // The last layer's activation is written NCHW-flat straight into the dense layer's input rows flat ([B][ldflat]):
     // nothing reads it in NHWC order (the backward of a layer reads its pre-BN map y and the activation below it).
     int enc_fwd(hipStream_t s, bool train, const float* audio_in, int B, T* flat, int ldflat) {
-        int h = enc.H, w = enc.W;
         HLMC_CHECK_ARG(audio_in, "audio input required");
         const float* audio = audio_in;
         enc.audio = audio_in;
@@ -603,6 +625,7 @@ class NetT : public NetBase {
         ops::BnInput xin{};
         for (int l = 0; l < 6; ++l) {
             const int ci = ENC_CH[l], co = ENC_CH[l + 1];
+            const int h = enc.rows(l), w = enc.cols(l), ho = enc.rows(l + 1), wo = enc.cols(l + 1);
             T* y = AT(enc.y[l]);
             // train mode: BN statistics from the producing conv's epilogue
             ops::ColStats st{train ? acc_fwd(enc.bb[l]) : XAcc{}, false};
@@ -611,17 +634,15 @@ class NetT : public NetBase {
             else
                 HLMC_TRY(ops::conv_s2<T>(s, fused_prev ? AT(enc.y[l - 1]) : AT(enc.a[l - 1]), B, h, w, ci, P0(enc.w[l]),
                                          P[enc.b[l]], co, y, scratch, &st, fused_prev ? &xin : nullptr));
-            h /= 2;
-            w /= 2;
-            const int64_t R = (int64_t)B * h * w;
-            fused_prev = train && l + 1 < 6 && ops::conv_s2_takes_input_bn<T>(B, h, w, co, ENC_CH[l + 2]);
+            const int64_t R = (int64_t)B * ho * wo;
+            fused_prev = train && l + 1 < 6 && ops::conv_s2_takes_input_bn<T>(B, ho, wo, co, ENC_CH[l + 2]);
             if (fused_prev) {
                 if (!st.done) HLMC_TRY(ops::bn_moments<T>(s, y, R, co, acc_fwd(enc.bb[l])));  // e.g. a split-K producer
                 xin = bn_input(enc.bb[l], enc.bn[l], enc.g[l], enc.beta[l], R, enc.a[l]);
             } else if (l == 5) {
                 const ops::FlatOut fo{ldflat, nullptr};
                 HLMC_TRY(bn_fwd(s, train, y, R, co, enc.bn[l], enc.bb[l], enc.g[l], enc.beta[l], 0, nullptr, 1.f, flat, 0,
-                                &st, &fo, h * w));
+                                &st, &fo, ho * wo));
             } else
                 HLMC_TRY(bn_fwd(s, train, y, R, co, enc.bn[l], enc.bb[l], enc.g[l], enc.beta[l], 0, nullptr, 1.f,
                                 AT(enc.a[l]), co, &st));
@@ -633,34 +654,26 @@ class NetT : public NetBase {
     int enc_bwd(hipStream_t s, int B, T* gA, int bucket_hi = -1) {
         const float* audio = enc.audio;
         HLMC_CHECK_ARG(audio, "backward: no forward input recorded");
-        int hs[7], ws_[7];
-        hs[0] = enc.H;
-        ws_[0] = enc.W;
-        for (int l = 0; l < 6; ++l) { hs[l + 1] = hs[l] / 2; ws_[l + 1] = ws_[l] / 2; }
         for (int l = 5; l >= 0; --l) {
             const int ci = ENC_CH[l], co = ENC_CH[l + 1];
-            const int ho = hs[l + 1], wo = ws_[l + 1];
+            const int ho = enc.rows(l + 1), wo = enc.cols(l + 1);
             const int64_t R = (int64_t)B * ho * wo;
             T* dy = AT(enc.dy[l]);
+            PendingBias pb;  // the conv bias gradient: written by the weight gradient's reduce launch
             HLMC_TRY(bn_bwd(s, gA, co, AT(enc.y[l]), R, co, enc.bb[l], enc.g[l], enc.beta[l], 0, nullptr, 1.f, dy, enc.b[l],
-                            nullptr, true, true));
+                            nullptr, &pb));
             float* gw = G[enc.w[l]];
             if (l == 0) {
                 // the last weight gradient of backward: on the main stream, which would otherwise only wait for
                 // the weight-gradient stream here (that stream is still reducing layer 1's gradient)
-                const PendingBias pb = pend_bias;
-                pend_bias = PendingBias{};
                 if (pb.gb) HLMC_TRY(ops::colsum_finalize(s, pb.acc, pb.C, pb.gb));
                 HLMC_TRY(ops::wgrad_c1<T>(s, dy, B, ho, wo, co, audio, gw, scratch));
-            } else if (l == 0) {
-                HLMC_TRY(side_bias(s, [=](hipStream_t q, Ws sc) { return ops::wgrad_c1<T>(q, dy, B, ho, wo, co, audio, gw, sc); }));
             } else {
                 const T* xin = AT(enc.a[l - 1]);
-                const PendingBias pb = take_bias();  // written by the weight gradient's reduce launch
-                HLMC_TRY(side_bias(s, [=](hipStream_t q, Ws sc) {
+                HLMC_TRY(wq.queue(s, [=](hipStream_t q, Ws sc) {
                     return ops::wgrad_s2<T>(q, dy, B, ho, wo, co, xin, ci, gw, sc, pb.acc, pb.gb);
-                }));
-                if (l == 1) HLMC_TRY(flush_side(s));  // nothing queued may wait for the join behind the main tail
+                }, side_batch()));
+                if (l == 1) HLMC_TRY(wq.flush(s));  // nothing queued may wait for the join behind the main tail
                 // grad of layer l-1's activation
                 HLMC_TRY(ops::subpixel<T>(s, dy, B, ho, wo, co, P1(enc.w[l]), nullptr, ci, gA, scratch));
             }
@@ -674,6 +687,8 @@ class NetT : public NetBase {
     struct Dec {
         int w[6], b[6], g[5], beta[5], bn[5];
         int h0 = 0, w0 = 0;  // low-res input grid (H/64, W/64)
+        int rows(int l) const { return h0 << l; }  // layer l's input grid: doubled per layer
+        int cols(int l) const { return w0 << l; }
         size_t y[5], a[5], dy[5];
         BnBufs bb[5];
     };
@@ -694,9 +709,9 @@ class NetT : public NetBase {
         }
     }
     void dec_plan(Arena& A, int64_t B) {
-        int h = dec.h0, w = dec.w0;
         for (int l = 0; l < 6; ++l) {
             const int ci = DEC_CH[l], co = DEC_CH[l + 1];
+            const int h = dec.rows(l), w = dec.cols(l);
             if (l < 5) {
                 need(ops::subpixel_ws<T>((int)B, h, w, ci, co));
                 need(ops::conv_s2_ws<T>((int)B, 2 * h, 2 * w, co, ci));
@@ -710,19 +725,17 @@ class NetT : public NetBase {
                 need(ops::wgrad_c1_ws((int)B, h, w, ci));
                 need(ops::colsum_ws((int)(B * 4 * h * w), 1));
             }
-            h *= 2;
-            w *= 2;
         }
     }
-    size_t dec_max_elems(int64_t B) const { return (size_t)B * dec.h0 * 32 * dec.w0 * 32 * 32; }
+    size_t dec_max_elems(int64_t B) const { return (size_t)B * dec.rows(5) * dec.cols(5) * 32; }
     // u: NHWC [B, h0, w0, 512]; recon f32 [B, 64 h0, 64 w0]
     int dec_fwd(hipStream_t s, bool train, const T* u, int B, float* recon) {
-        int h = dec.h0, w = dec.w0;
         const T* x = u;
         bool fused_prev = false;  // layer l-1's BatchNorm + activation is applied inside layer l's sub-pixel conv
         ops::BnInput xin{};
         for (int l = 0; l < 6; ++l) {
             const int ci = DEC_CH[l], co = DEC_CH[l + 1];
+            const int h = dec.rows(l), w = dec.cols(l);
             if (l < 5) {
                 T* y = AT(dec.y[l]);
                 const int64_t R = (int64_t)B * 4 * h * w;
@@ -740,49 +753,43 @@ class NetT : public NetBase {
             } else {
                 HLMC_TRY(ops::convT_c1<T>(s, x, B, h, w, ci, P[dec.w[5]], P[dec.b[5]], recon));
             }
-            h *= 2;
-            w *= 2;
         }
         return HLMC_OK;
     }
     // gA: data-gradient chain buffer.  The grad wrt u is written NCHW-flat to gflat ([B][ldflat]: the operand of the
     // dense layer below), zeroed where relu_ref (nullable: u, when it is a ReLU's output) is not positive
     int dec_bwd(hipStream_t s, const T* u, int B, const float* d_recon, T* gA, T* gflat, int ldflat, const T* relu_ref) {
-        int hs[7], ws_[7];
-        hs[0] = dec.h0;
-        ws_[0] = dec.w0;
-        for (int l = 0; l < 6; ++l) { hs[l + 1] = hs[l] * 2; ws_[l + 1] = ws_[l] * 2; }
-        // last layer (1 output channel): input a4 [B, hs5, ws5, 32]
+        // last layer (1 output channel): input a4 [B, rows(5), cols(5), 32]
         {
-            const int hl = hs[5], wl = ws_[5];
+            const int hl = dec.rows(5), wl = dec.cols(5);
             const T* a4 = AT(dec.a[4]);
             float* gw = G[dec.w[5]];
             float* gb = G[dec.b[5]];
-            const int npix = B * hs[6] * ws_[6];
-            HLMC_TRY(side(s, [=](hipStream_t q, Ws sc) {
+            const int npix = B * dec.rows(6) * dec.cols(6);
+            HLMC_TRY(wq.run(s, [=](hipStream_t q, Ws sc) {
                 HLMC_TRY(ops::wgrad_c1<T>(q, a4, B, hl, wl, DEC_CH[5], d_recon, gw, sc));
                 return ops::colsum<float>(q, d_recon, 1, npix, 1, gb, sc);
             }));
             // layer 4's BN-backward moments come with the edge conv that writes its output gradient
             fuse4 = ops::BnBwdFuse{AT(dec.y[4]), AF(dec.bb[4].mean), AF(dec.bb[4].inv), P[dec.g[4]], P[dec.beta[4]],
                                    acc_mom(dec.bb[4]), false};
-            HLMC_TRY(ops::conv_c1_s2<T>(s, d_recon, B, hs[6], ws_[6], P[dec.w[5]], nullptr, DEC_CH[5], gA, nullptr,
+            HLMC_TRY(ops::conv_c1_s2<T>(s, d_recon, B, dec.rows(6), dec.cols(6), P[dec.w[5]], nullptr, DEC_CH[5], gA, nullptr,
                                         &fuse4));
         }
         ops::BnBwdFuse fuse = fuse4;
         for (int l = 4; l >= 0; --l) {
             const int ci = DEC_CH[l], co = DEC_CH[l + 1];
-            const int hl = hs[l], wl = ws_[l];
+            const int hl = dec.rows(l), wl = dec.cols(l);
             const int64_t R = (int64_t)B * 4 * hl * wl;
             T* dy = AT(dec.dy[l]);
+            PendingBias pb;  // the conv bias gradient: written by the weight gradient's reduce launch
             HLMC_TRY(bn_bwd(s, gA, co, AT(dec.y[l]), R, co, dec.bb[l], dec.g[l], dec.beta[l], 0, nullptr, 1.f, dy, dec.b[l],
-                            &fuse, true, true));
+                            &fuse, &pb));
             const T* xin = l == 0 ? u : AT(dec.a[l - 1]);
             float* gw = G[dec.w[l]];
-            const PendingBias pb = take_bias();  // written by the weight gradient's reduce launch
-            HLMC_TRY(side_bias(s, [=](hipStream_t q, Ws sc) {
+            HLMC_TRY(wq.queue(s, [=](hipStream_t q, Ws sc) {
                 return ops::wgrad_s2<T>(q, xin, B, hl, wl, ci, dy, co, gw, sc, pb.acc, pb.gb);
-            }));
+            }, side_batch()));
             const ops::FlatOut fo{ldflat, relu_ref};
             HLMC_TRY(ops::conv_s2<T>(s, dy, B, 2 * hl, 2 * wl, co, P0(dec.w[l]), nullptr, ci, l == 0 ? gflat : gA, scratch,
                                      nullptr, nullptr, l == 0 ? &fo : nullptr));
@@ -946,13 +953,7 @@ class HybridNet : public NetT<T> {
 
     int forward(hipStream_t s, const ForwardArgs& a) override {
         const int B = (int)a.B;
-        HLMC_CHECK_ARG(B >= 2 || !a.train, "BatchNorm in train mode needs batch >= 2");
-        this->ws_bytes(B);
-        this->set_ws(a.ws);
-        HLMC_TRY(this->settle(s));
-        HLMC_TRY(this->pack_all(s));
-        if (a.train) HLMC_TRY(this->zero_acc_fwd(s));
-        this->last_full_forward = !a.encode_only && !a.decode_only;
+        HLMC_TRY(this->begin_forward(s, a));
         if (a.decode_only) {  // decode(z), src/Convolutional_VAE.py:167-179
             HLMC_CHECK_ARG(a.in0 && a.recon, "z and recon required");
             HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, L, AT(z_), L, B, L));
@@ -980,12 +981,7 @@ class HybridNet : public NetT<T> {
 
     int backward(hipStream_t s, const BackwardArgs& a) override {
         const int B = (int)a.B;
-        HLMC_CHECK_ARG(B == this->planned_B, "backward batch differs from the last forward");
-        HLMC_CHECK_ARG(this->last_full_forward, "backward needs a full hlmc_net_forward (not encode / decode)");
-        this->set_ws(a.ws);
-        HLMC_TRY(this->side_init());
-        HLMC_TRY(this->settle(s));
-        HLMC_TRY(this->zero_acc_bwd(s));
+        HLMC_TRY(this->begin_backward(s, a));
         T* gA = AT(gA_);
         // ---- text decoder
         if (text) {
@@ -1136,13 +1132,7 @@ class CvaeNet : public NetT<T> {
 
     int forward(hipStream_t s, const ForwardArgs& a) override {
         const int B = (int)a.B;
-        HLMC_CHECK_ARG(B >= 2 || !a.train, "BatchNorm in train mode needs batch >= 2");
-        this->ws_bytes(B);
-        this->set_ws(a.ws);
-        HLMC_TRY(this->settle(s));
-        HLMC_TRY(this->pack_all(s));
-        if (a.train) HLMC_TRY(this->zero_acc_fwd(s));
-        this->last_full_forward = !a.encode_only && !a.decode_only;
+        HLMC_TRY(this->begin_forward(s, a));
         if (a.decode_only) {  // decode(z, condition), src/Conditional_VAE.py:206-225
             HLMC_CHECK_ARG(a.in0 && a.in2 && a.recon && a.recon_text, "z / condition / recon / recon_text required");
             HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, L, AT(Z_), ldZ, B, L));
@@ -1165,13 +1155,8 @@ class CvaeNet : public NetT<T> {
 
     int backward(hipStream_t s, const BackwardArgs& a) override {
         const int B = (int)a.B;
-        HLMC_CHECK_ARG(B == this->planned_B, "backward batch differs from the last forward");
-        HLMC_CHECK_ARG(this->last_full_forward, "backward needs a full hlmc_net_forward (not encode / decode)");
         HLMC_CHECK_ARG(a.d_recon_text, "d_recon_text required");
-        this->set_ws(a.ws);
-        HLMC_TRY(this->side_init());
-        HLMC_TRY(this->settle(s));
-        HLMC_TRY(this->zero_acc_bwd(s));
+        HLMC_TRY(this->begin_backward(s, a));
         T* gA = AT(gA_);
         // text decoder
         HLMC_TRY(ops::cast2d_from_f32<T>(s, a.d_recon_text, TD, AT(grt_), ldT, B, TD));
@@ -1304,14 +1289,19 @@ class SimpleNet : public NetT<T> {
     const uint8_t* mask_of(const Blk& b) const { return dropout ? dropout + b.mask_off : nullptr; }
     const uint8_t* dropout = nullptr;
     static constexpr float kKeepScale = 1.f / 0.8f;  // Dropout(0.2)
-
-    int encode(hipStream_t s, const ForwardArgs& a, int B) {
-        const bool tr = a.train != 0;
+    // train mode: the caller's mask bytes are copied into the workspace (backward reads them again)
+    int stage_dropout(hipStream_t s, const ForwardArgs& a) {
         dropout = nullptr;
-        if (tr && a.dropout) {
+        if (a.train && a.dropout) {
             HLMC_HIP(hipMemcpyAsync(AU8(mask_), a.dropout, (size_t)mask_total, hipMemcpyDeviceToDevice, s));
             dropout = AU8(mask_);
         }
+        return HLMC_OK;
+    }
+
+    int encode(hipStream_t s, const ForwardArgs& a, int B) {
+        const bool tr = a.train != 0;
+        HLMC_TRY(stage_dropout(s, a));
         HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, D, AT(x_), ldD, B, D));
         const T* x = AT(x_);
         int ldx = ldD;
@@ -1329,20 +1319,10 @@ class SimpleNet : public NetT<T> {
 
     int forward(hipStream_t s, const ForwardArgs& a) override {
         const int B = (int)a.B;
-        HLMC_CHECK_ARG(B >= 2 || !a.train, "BatchNorm in train mode needs batch >= 2");
-        this->ws_bytes(B);
-        this->set_ws(a.ws);
-        HLMC_TRY(this->settle(s));
-        HLMC_TRY(this->pack_all(s));
-        if (a.train) HLMC_TRY(this->zero_acc_fwd(s));
-        this->last_full_forward = !a.encode_only && !a.decode_only;
+        HLMC_TRY(this->begin_forward(s, a));
         if (a.decode_only) {  // decode(z), src/Simple_VAE.py:95-96 (decoder blocks' dropout from the same mask layout)
             HLMC_CHECK_ARG(a.in0 && a.recon, "z and recon required");
-            dropout = nullptr;
-            if (a.train && a.dropout) {
-                HLMC_HIP(hipMemcpyAsync(AU8(mask_), a.dropout, (size_t)mask_total, hipMemcpyDeviceToDevice, s));
-                dropout = AU8(mask_);
-            }
+            HLMC_TRY(stage_dropout(s, a));
             HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, L, AT(z_), pad8(L), B, L));
         } else {
             HLMC_TRY(encode(s, a, B));
@@ -1367,12 +1347,7 @@ class SimpleNet : public NetT<T> {
 
     int backward(hipStream_t s, const BackwardArgs& a) override {
         const int B = (int)a.B;
-        HLMC_CHECK_ARG(B == this->planned_B, "backward batch differs from the last forward");
-        HLMC_CHECK_ARG(this->last_full_forward, "backward needs a full hlmc_net_forward (not encode / decode)");
-        this->set_ws(a.ws);
-        HLMC_TRY(this->side_init());
-        HLMC_TRY(this->settle(s));
-        HLMC_TRY(this->zero_acc_bwd(s));
+        HLMC_TRY(this->begin_backward(s, a));
         T* g1 = AT(gx1_);
         HLMC_TRY(ops::cast2d_from_f32<T>(s, a.d_recon, D, AT(grec_), ldD, B, D));
         const Blk& last = decb.back();
@@ -1400,7 +1375,7 @@ class SimpleNet : public NetT<T> {
             const int ldx = i == 0 ? ldD : encb[i - 1].dout;
             HLMC_TRY(this->lin_bwd(s, dy, b.dout, xin, ldx, B, b.w, -1, i == 0 ? nullptr : g1, b.din));
         }
-        HLMC_TRY(this->join(s));
+        HLMC_TRY(this->wq.join(s));
         return this->mark(s, 0);
     }
 };
