@@ -518,10 +518,6 @@ int hlmc_op_wgrad_c1(void* stream, int dtype, const void* Lo, int B, int Hl, int
                        ops::wgrad_c1<bf16>(S(stream), (const bf16*)Lo, B, Hl, Wl, M, Xh, dW, w));
 }
 
-// LDS halo-tile forward (conv_s2 / subpixel, bf16) with the train-mode epilogue statistics and, when gamma is given,
-// the layer below's BatchNorm + LeakyReLU(0.01) applied while the input is staged (the engine's BnInput path):
-// x is then the pre-BN map, whose exact statistics this entry first accumulates with the moments pass the engine's
-// producers would have delivered.  out_sums[2 Co] = (sum y | sum y^2) over the stored bf16 outputs.
 int64_t hlmc_op_bn_bwd_workspace(int C) {
     if (C <= 0) return 0;
     return (int64_t)(((ops::bn_acc_bytes(C) + 255) & ~(size_t)255) + ((ops::bias_acc_bytes(C) + 255) & ~(size_t)255) +
@@ -547,6 +543,10 @@ int hlmc_op_bn_bwd(void* stream, int dtype, const void* da, const void* y, int64
         ops::bn_act_bwd<bf16>(s, (const bf16*)da, C, (const bf16*)y, R, C, mean, invstd, gamma, beta, 0, nullptr, 1.f,
                               (bf16*)dy, dgamma, dbeta, mom, nullptr, dbias ? bacc : XAcc{}, dbias, sums));
 }
+// LDS halo-tile forward (conv_s2 / subpixel, bf16) with the train-mode epilogue statistics and, when gamma is given,
+// the layer below's BatchNorm + LeakyReLU(0.01) applied while the input is staged (the engine's BnInput path):
+// x is then the pre-BN map, whose exact statistics this entry first accumulates with the moments pass the engine's
+// producers would have delivered.  out_sums[2 Co] = (sum y | sum y^2) over the stored bf16 outputs.
 static size_t halo_acc_off(int Ci) { return (XAcc::bytes(xacc_shards(Ci), 2 * Ci) + 255) & ~(size_t)255; }
 int64_t hlmc_op_halo_workspace(int Ci, int Co) {
     return (int64_t)(halo_acc_off(Ci) + XAcc::bytes(xacc_shards(Co), 2 * Co));

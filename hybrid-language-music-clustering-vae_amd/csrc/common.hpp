@@ -304,6 +304,49 @@ __device__ __forceinline__ void xacc_fold(const XAcc& x, double* out, long long*
     __syncthreads();
 }
 
+// ------------------------------------------------------------------ train-mode BatchNorm finalize
+// One channel's batch statistics from its totals s = sum y, q = sum y^2 over R rows (f64): mean, invstd of the
+// biased variance (clamped at 0), and, where rmean is given, the channel's running pair blended in place with the
+// unbiased variance (torch's BatchNorm2d).  The one statement of this arithmetic: bn_finalize_kernel and the
+// consumer-side finalizes (kernels.hip bn_fin_prologue, halo.hpp bn_in_prologue) call it.
+__device__ __forceinline__ void bn_train_finalize(double s, double q, int64_t R, float eps, float momentum, float& mean,
+                                                  float& invstd, float* rmean, float* rvar) {
+    const double m = s / (double)R;
+    double var = q / (double)R - m * m;
+    if (var < 0.0) var = 0.0;
+    mean = (float)m;
+    invstd = (float)(1.0 / sqrt(var + (double)eps));
+    if (rmean) {
+        const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
+        *rmean = (float)((1.0 - momentum) * *rmean + momentum * m);
+        *rvar = (float)((1.0 - momentum) * *rvar + momentum * unb);
+    }
+}
+// The forward side of a consumer-side finalize: the producer's exact accumulator (2C columns: sum | sum of squares)
+// and where block 0 stores what later kernels read.
+struct BnTrainFwd {
+    XAcc acc;
+    int64_t R = 0;  // rows of the normalised map
+    float *mean = nullptr, *invstd = nullptr, *rmean = nullptr, *rvar = nullptr;
+    int64_t* nbt = nullptr;
+    float momentum = 0.f, eps = 0.f;
+};
+// channel c of a block that finalizes for itself: every block computes mean / invstd, block 0 also stores them,
+// blends the running statistics and counts the batch
+__device__ __forceinline__ void bn_train_channel(const BnTrainFwd& f, int c, double s, double q, float& mean,
+                                                 float& invstd) {
+    const bool first = blockIdx.x == 0, run = first && f.rmean;
+    float m, inv;
+    bn_train_finalize(s, q, f.R, f.eps, f.momentum, m, inv, run ? f.rmean + c : nullptr, run ? f.rvar + c : nullptr);
+    mean = m;
+    invstd = inv;
+    if (first) {
+        f.mean[c] = m;
+        f.invstd[c] = inv;
+        if (c == 0 && f.nbt) f.nbt[0] += 1;
+    }
+}
+
 // wave-level sums (wave64)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

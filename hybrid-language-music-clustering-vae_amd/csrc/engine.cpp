@@ -612,7 +612,7 @@ class NetT : public NetBase {
     // train-mode BatchNorm + LeakyReLU of layer l's output applied by the next conv while it stages its input
     // (ops::BnInput: the LDS halo-tile kernels) instead of a bn_act pass; the activation is written by that kernel
     ops::BnInput bn_input(const BnBufs& bb, int bn, int g, int beta, int64_t R, size_t a_off) {
-        return ops::BnInput{acc_fwd(bb), R, AF(bb.mean), AF(bb.inv), RM[bn], RV[bn], NBT[bn], kBnMomentum, kBnEps,
+        return ops::BnInput{{acc_fwd(bb), R, AF(bb.mean), AF(bb.inv), RM[bn], RV[bn], NBT[bn], kBnMomentum, kBnEps},
                             P[g], P[beta], ws + a_off};
     }
     // The last layer's activation is written NCHW-flat straight into the dense layer's input rows flat ([B][ldflat]):

@@ -1,5 +1,6 @@
 // Launchers for the MFMA GEMM families (tile choice + deterministic split-K planning).
 #include "gemm.hpp"
+#include "halo.hpp"
 #include "ops.hpp"
 
 #include <algorithm>
@@ -431,486 +432,92 @@ size_t dispatch_tn_ws(int M, int N, int K) {
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline int log2_exact(int c) { return (c > 0 && (c & (c - 1)) == 0) ? __builtin_ctz(c) : -1; }
 
-// The epilogue of the persistent halo kernels: the block's bias columns from an LDS table (filled once before the
-// tile loop) and stores without the accumulate read, so the tile loop issues no global loads besides the prefetched
-// input rows.  (With the per-tile bias / accumulate loads in the loop the compiler's wait-count merge at the loop
-// head waited for ALL outstanding loads -- the prefetch included -- before the first MFMA of every tile.)
+// ---- the LDS halo-tile kernels (halo.hpp) and their four shapes (bf16).  A row: the shape (Hi a multiple of hdiv:
+// whole tiles per image), the tile's pixels (GEMM rows: output pixels of the conv, low-res pixels of the sub-pixel
+// conv), and per form the channel splits (blocks per tile) and the grid cap, with the kernels built for them.  The
+// statistics and input-BatchNorm forms share a tiling; the plain form (data gradients, eval) may differ.
+struct HaloGrid {
+    int nspl, cap;
+};
 template <class EP>
-struct HaloEp : EP {
-    const float* lb;  // LDS: bias of columns nbase ..
-    int nbase;
-    __device__ float colbias(int n) const { return lb[n - nbase]; }
-    __device__ float put(int64_t ro, int n, float v) const { return EP::put_na(ro, n, v); }
-    __device__ void put4(int64_t ro, int n, float (&v)[4]) const { EP::put4_na(ro, n, v); }
+struct HaloShape {
+    using Plain = void (*)(const bf16*, int, int, const bf16*, EP, int, ops::BnInput);
+    using Stats = void (*)(const bf16*, int, int, const bf16*, WithStats<EP>, int, ops::BnInput);
+    int Ci, Co, Wi, hdiv, tp;
+    HaloGrid stat, plain;
+    Plain k_plain;
+    Stats k_stats, k_xin;
 };
-
-// ---- train-mode BatchNorm + LeakyReLU(0.01) of a halo kernel's INPUT, applied while its rows are staged (XIN):
-// the input pointer is the pre-BN map y of the layer below; the block folds that layer's statistics accumulator
-// in its prologue (bn_act_train's consumer-side finalize, same arithmetic; block 0 stores mean / invstd / running
-// statistics), transforms each staged 16-byte chunk (8 channels) in registers, and writes the activation a of the
-// rows its tile owns (every input row exactly once over the grid, by the first channel-split block) for the weight
-// gradient that reads it later.  Rows outside the image stay zero (padding).
-struct BnIn {
-    XAcc acc;                       // 2C columns
-    int64_t R;                      // rows of the normalised map
-    float *mean, *invstd, *rmean, *rvar;
-    int64_t* nbt;
-    float momentum, eps;
-    const float *gamma, *beta;
-    bf16* a_out;
+template <class G, class EP, int WPE, class GP = G, int WPE_P = WPE>  // GP / WPE_P: the plain form's, where it differs
+constexpr HaloShape<EP> halo_shape(int hdiv, int cap, int cap_p) {
+    return {G::CI, G::CO, G::WI, hdiv, G::TP, {G::NSPL, cap}, {GP::NSPL, cap_p}, halo_kernel<GP, EP, false, WPE_P>,
+            halo_kernel<G, WithStats<EP>, false, WPE>, halo_kernel<G, WithStats<EP>, true, WPE>};
+}
+using ConvEp = StoreRM<bf16>;
+using SubEp = StoreSubpixel<bf16>;
+// Two blocks per CU (WPE 2, a 512-block grid) where a block fits in half the LDS (<= 80 KB) and 256 VGPRs: the
+// co-resident block covers the single halo buffer's extra barrier.
+// conv 32 -> 64, Wi 64: 2-row (64-pixel) tiles: 64 KB (73 KB with the input BatchNorm).  Measured in
+// the step: forward with the input BatchNorm + statistics 49.6 -> 42.7 us, the decoder data gradient 32.2 -> 31.5 us
+// (4-row tiles, two halo buffers, one block per CU before); the same with 4-row tiles and two 32-channel blocks per
+// tile (the halo read twice) lost (50 -> 55 / 32 -> 36 us).
+// conv 64 -> 128, Wi 32: two 64-channel halves per 64-pixel tile (the weights take half the LDS), one block per CU.
+constexpr HaloShape<ConvEp> kConvHalo[] = {
+    halo_shape<ConvS2Halo<32, 64, 1, 32, 2>, ConvEp, 2>(8, 512, 512),
+    halo_shape<ConvS2Halo<64, 64, 2, 16, 4>, ConvEp, 1>(8, 256, 256),
 };
-template <int CI>
-struct BnInLds {  // prologue scratch + per-channel parameters (LDS)
-    double tot[2 * CI];
-    long long red[3 * 256];
-    float prm[4 * CI];  // mean | invstd | gamma | beta
+// sub-pixel 64 -> 32, Wi 32, all three forms two per CU: 129.3k vs 128.0k clips/s, 3 alternating rounds (forward
+// 53 -> 46 us, data gradient 72 -> 56 us in the step).
+// sub-pixel 128 -> 64, Wi 16: the plain form (data gradient) with 16 channels per block (four blocks per tile,
+// 79 KB) two per CU 38 -> 33 us, while its statistics / input-BN forms would need 90 KB (one block per CU) and lost
+// 48 -> 68 us: they keep 32 channels per block.
+constexpr HaloShape<SubEp> kSubpixelHalo[] = {
+    halo_shape<SubpixelHalo<64, 32, 1, 32, 4>, SubEp, 2>(4, 512, 512),
+    halo_shape<SubpixelHalo<128, 32, 2, 16, 8>, SubEp, 1, SubpixelHalo<128, 16, 4, 16, 8>, 2>(8, 256, 512),
 };
-template <int CI>
-__device__ __forceinline__ void bn_in_prologue(const BnIn& f, BnInLds<CI>& L) {
-    xacc_fold(f.acc, L.tot, L.red);
-    for (int c = threadIdx.x; c < CI; c += 256) {
-        const double m = L.tot[c] / (double)f.R;
-        double var = L.tot[CI + c] / (double)f.R - m * m;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)m, inv = (float)(1.0 / sqrt(var + (double)f.eps));
-        L.prm[c] = mf;
-        L.prm[CI + c] = inv;
-        L.prm[2 * CI + c] = f.gamma[c];
-        L.prm[3 * CI + c] = f.beta[c];
-        if (blockIdx.x == 0) {
-            f.mean[c] = mf;
-            f.invstd[c] = inv;
-            if (f.rmean) {
-                const double unb = f.R > 1 ? var * (double)f.R / (double)(f.R - 1) : var;
-                f.rmean[c] = (float)((1.0 - f.momentum) * f.rmean[c] + f.momentum * m);
-                f.rvar[c] = (float)((1.0 - f.momentum) * f.rvar[c] + f.momentum * unb);
-            }
-            if (c == 0 && f.nbt) f.nbt[0] += 1;
-        }
-    }
-    __syncthreads();
+template <class EP, size_t N>
+const HaloShape<EP>* halo_find(const HaloShape<EP> (&tab)[N], int Ci, int Co, int Wi, int Hi) {
+    for (const HaloShape<EP>& h : tab)
+        if (h.Ci == Ci && h.Co == Co && h.Wi == Wi && Hi % h.hdiv == 0) return &h;
+    return nullptr;
 }
-// lrelu((x - mean) * invstd * gamma + beta) of 8 bf16 channels (the thread's parameters in registers)
-__device__ __forceinline__ uint4 bn_in_apply(uint4 v, const float (&pr)[4][8]) {
-    float x[8];
-    cvt16_f32<bf16>(v, x);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float z = (x[k] - pr[0][k]) * pr[1][k] * pr[2][k] + pr[3][k];
-        x[k] = z > 0.f ? z : 0.01f * z;
+// One launch over the M / tp tiles (whole rows: tiles stay inside an image): the statistics form (with the input
+// BatchNorm when xin is given) when st has an accumulator, which it then marks delivered, else the plain form.
+template <class EP>
+int halo_launch(hipStream_t s, const HaloShape<EP>& h, const bf16* x, int Hi, const bf16* wp, const EP& ep, int M,
+                ops::ColStats* st, const ops::BnInput* xin) {
+    const int ntiles = M / h.tp;
+    const bool stats = st && st->acc.on();
+    const HaloGrid g = stats ? h.stat : h.plain;
+    const int grid = std::min(ntiles * g.nspl, g.cap);
+    HLMC_PROBE_BEGIN(s);
+    if (stats) {
+        WithStats<EP> eps;
+        static_cast<EP&>(eps) = ep;
+        eps.acc = st->acc;
+        (xin ? h.k_xin : h.k_stats)<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, eps, M, xin ? *xin : ops::BnInput{});
+    } else {
+        h.k_plain<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, ep, M, ops::BnInput{});
     }
-    uint4 o;
-    unsigned* w = reinterpret_cast<unsigned*>(&o);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        bf16 lo = __float2bfloat16(x[2 * i]), hi = __float2bfloat16(x[2 * i + 1]);
-        w[i] = (unsigned)(*reinterpret_cast<unsigned short*>(&lo)) | ((unsigned)(*reinterpret_cast<unsigned short*>(&hi)) << 16);
-    }
-    return o;
+    if (st) st->done = stats;
+    HLMC_PROBE_END(s);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
 }
-
-// ---- stride-2 3x3 conv over LDS halo tiles: Ci = 32, Wo = 32, bf16, Co = CO.
-// Measured (scripts/bench_gemm.py): the 64x64x32 -> 64 conv and the matching decoder data gradient 46.3 / 44.1 ->
-// 36.7 / 34.2 us; bench A/B 106.4k vs 105.0k clips/s (3 alternating rounds).
-// A persistent block (one per CU) keeps the packed weights [CO][9 x 32] in LDS and walks 128-pixel M-tiles (4
-// output rows of one image).  Each tile's 9 input rows (plus the zero column left of the image) are staged in
-// LDS once, and every tap's A fragment is read from there: the input crosses L2 once per tile instead of once
-// per (tap, 16-byte chunk) gather.  The next tile's rows are loaded into registers while this tile computes.
-// Template: CI input channels, COB output channels per block (NSPL blocks share a tile's Co = NSPL * COB), WO
-// output width, ROWS output rows per tile (TP = ROWS * WO pixels), DB: double-buffered halo (else one buffer and
-// an extra barrier).  Shapes: 2 WO * CI / 8 == 256 (one 16-byte chunk per thread per input row).
-template <int CI, int COB, int NSPL, int WO, int ROWS, bool DB, class EP, bool TR = true, bool XIN = false, int WPE = 1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void conv_s2_halo_kernel(const bf16* __restrict__ x, int Hi, int ntiles,
-                                                           const bf16* __restrict__ wp, EP ep, int M, BnIn xin) {
-    constexpr int WI = 2 * WO, HR = 2 * ROWS + 1, HC = WI + 1, PS = CI + 8;  // halo rows / cols / pixel pitch
-    constexpr int TP = ROWS * WO, CPP = CI / 8;                             // tile pixels, chunks per pixel
-    static_assert(WI * CPP == 256 && (COB == 64 || COB == 32), "halo chunk map / wave tiling");
-    constexpr int KP = 9 * CI + 8;      // weight row: 16 n-rows of a fragment read on distinct 16-byte slots
-    constexpr int HS = HR * HC * PS;    // one halo buffer (bf16)
-    constexpr int WAVES_N = COB / 32;   // 4 waves: 2 x 2 over (TP x 64) or 4 x 1 over (TP x 32)
-    constexpr int WM = TP / (4 / WAVES_N), WN = 32, TM = WM / 16, TN = 2;
-    static_assert(WM % 16 == 0, "wave rows");
-    constexpr int CO = NSPL * COB;
-    __shared__ __attribute__((aligned(16))) bf16 Bs[COB * KP];
-    __shared__ __attribute__((aligned(16))) bf16 Hs[(DB ? 2 : 1) * HS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm0 = (wave / WAVES_N) * WM, wn0 = (wave % WAVES_N) * WN;
-    const int tpi = (Hi / 2) / ROWS;   // tiles per image
-    const int nh = blockIdx.x % NSPL, n0 = nh * COB;
-    const int bstep = gridDim.x / NSPL;
-    __shared__ float bsh[COB];  // this block's bias columns
-    if (tid < COB) bsh[tid] = n0 + tid < CO ? ep.colbias(n0 + tid) : 0.f;
-    HaloEp<EP> hep;
-    static_cast<EP&>(hep) = ep;
-    hep.lb = bsh;
-    hep.nbase = n0;
-    for (int c = tid; c < COB * 9 * CPP; c += 256) {  // this block's weight rows
-        const int n = c / (9 * CPP), q = c - n * (9 * CPP);
-        *reinterpret_cast<uint4*>(&Bs[n * KP + q * 8]) =
-            *reinterpret_cast<const uint4*>(wp + (int64_t)(n0 + n) * 9 * CI + q * 8);
-    }
-    for (int c = tid; c < (DB ? 2 : 1) * HR * CPP; c += 256) {  // the pad column (input column -1) stays zero
-        const int bufr = c / CPP, q = c - bufr * CPP;
-        *reinterpret_cast<uint4*>(&Hs[(bufr / HR) * HS + ((bufr % HR) * HC) * PS + q * 8]) = make_uint4(0, 0, 0, 0);
-    }
-    uint4 hr[HR];  // HR rows x 256 chunks / 256 threads
-    auto row_off = [&](int b, int ih) { return (((int64_t)b * Hi + ih) * WI + tid / CPP) * CI + (tid % CPP) * 8; };
-    // unconditional loads (row -1 clamped to row 0; zeroed when staged): a branch per row made the compiler wait
-    // for the loads right after issuing them
-    auto load_rows = [&](uint4* h, int t) {
-        const int b = t / tpi, oh0 = (t - b * tpi) * ROWS;
-#pragma unroll
-        for (int u = 0; u < HR; ++u) {
-            const int ih = 2 * oh0 - 1 + u;
-            h[u] = *reinterpret_cast<const uint4*>(x + row_off(b, ih < 0 ? 0 : ih));
-        }
-    };
-    float pr[XIN ? 4 : 1][8];  // XIN: this thread's 8 channels' BatchNorm parameters
-    // XIN: the rows of tile t become activations (in range: all but row -1); rows 2 oh0 .. are this tile's to write
-    auto xform_rows = [&](uint4* h, int t) {
-        if constexpr (XIN) {
-            const int b = t / tpi, oh0 = (t - b * tpi) * ROWS;
-#pragma unroll
-            for (int u = 0; u < HR; ++u) {
-                const int ih = 2 * oh0 - 1 + u;
-                if (ih < 0) continue;
-                h[u] = bn_in_apply(h[u], pr);
-                if (u > 0 && nh == 0) *reinterpret_cast<uint4*>(xin.a_out + row_off(b, ih)) = h[u];
-            }
-        }
-    };
-    auto store_rows = [&](const uint4* h, int buf, int t) {
-        const bool top = (t % tpi) == 0;  // the tile's row -1 is the zero padding above the image
-#pragma unroll
-        for (int u = 0; u < HR; ++u)
-            *reinterpret_cast<uint4*>(&Hs[buf * HS + (u * HC + tid / CPP + 1) * PS + (tid % CPP) * 8]) =
-                (u == 0 && top) ? make_uint4(0, 0, 0, 0) : h[u];
-    };
-    int t = blockIdx.x / NSPL, buf = 0;
-    if (t < ntiles) load_rows(hr, t);  // in flight during the statistics prologue
-    if constexpr (XIN) {
-        __shared__ BnInLds<CI> bl;
-        bn_in_prologue<CI>(xin, bl);
-        const int c0 = (tid % CPP) * 8;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            pr[0][k] = bl.prm[c0 + k];
-            pr[1][k] = bl.prm[CI + c0 + k];
-            pr[2][k] = bl.prm[2 * CI + c0 + k];
-            pr[3][k] = bl.prm[3 * CI + c0 + k];
-        }
-    }
-    if (t < ntiles) {
-        xform_rows(hr, t);
-        store_rows(hr, 0, t);
-    }
-    __syncthreads();
-    const int g8 = (lane >> 4) * 8;
-    // statistics (kStatMode 1): each lane's column sums over all its tiles in registers, reduced across the block
-    // once at the end (a per-tile LDS reduction cost two barriers per tile)
-    constexpr int NS = TR ? TN * 4 : TN;
-    double run_s[NS], run_q[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) run_s[j] = run_q[j] = 0.0;
-    constexpr int WAVES_M = 4 / WAVES_N;
-    __shared__ double sred[EP::kStatMode == 1 ? WAVES_M : 1][2][COB];
-    for (; t < ntiles; t += bstep) {
-        const int tn = t + bstep;
-        // in flight during this tile's MFMAs and stores; unconditional (clamped tile index, the last tile re-reads
-        // its own rows): with a conditional load the compiler cannot count the loads younger than the ones it must
-        // wait for and waits for all of them (measured with the bias / accumulate loads moved out of the loop:
-        // 36.6 -> 27.1 us for the 64 x 64 x 32 -> 64 conv; a second register set two tiles ahead: slower)
-        uint4* cur = hr;
-        load_rows(cur, min(tn, ntiles - 1));
-        f32x4_t acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        const bf16* H = Hs + buf * HS;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int kh = tap / 3, kw = tap % 3;
-#pragma unroll
-            for (int kc = 0; kc < CI / 32; ++kc) {
-                bf16x8_t af[TM], bfr[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const int m = wm0 + i * 16 + (lane & 15);
-                    const int hrow = 2 * (m / WO) + kh, hcol = 2 * (m % WO) + kw;  // (2oh-1+kh, 2ow-1+kw), col +1
-                    af[i] = *reinterpret_cast<const bf16x8_t*>(&H[(hrow * HC + hcol) * PS + kc * 32 + g8]);
-                }
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const int n = wn0 + j * 16 + (lane & 15);
-                    bfr[j] = *reinterpret_cast<const bf16x8_t*>(&Bs[n * KP + tap * CI + kc * 32 + g8]);
-                }
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)  // TR: operands swapped, channels x pixels (epilogue_tile_t)
-                        acc[i][j] = mfma_bf16<TR>(af[i], bfr[j], acc[i][j]);
-            }
-        }
-        double cs[TR ? TN * 4 : TN], cq[TR ? TN * 4 : TN];
-        if constexpr (TR)
-            epilogue_tile_t<TM, TN, HaloEp<EP>, true>(hep, acc, t * TP + wm0, n0 + wn0, lane, M, CO,
-                                              *reinterpret_cast<double(*)[TN][4]>(cs),
-                                              *reinterpret_cast<double(*)[TN][4]>(cq));
-        else
-            epilogue_tile<TM, TN>(hep, acc, t * TP + wm0, n0 + wn0, lane, M, CO, cs, cq);
-        if constexpr (EP::kStatMode == 1) {
-#pragma unroll
-            for (int j = 0; j < NS; ++j) {
-                run_s[j] += cs[j];
-                run_q[j] += cq[j];
-            }
-        }
-        if constexpr (DB) {
-            if (tn < ntiles) {
-                xform_rows(cur, tn);
-                store_rows(cur, buf ^ 1, tn);
-            }
-            __syncthreads();
-            buf ^= 1;
-        } else {
-            if (tn < ntiles) xform_rows(cur, tn);
-            __syncthreads();  // every wave is done with this tile's halo (and the statistics scratch)
-            if (tn < ntiles) store_rows(cur, 0, tn);
-            __syncthreads();
-        }
-    }
-    if constexpr (EP::kStatMode == 1) {
-        stats_to_lds<TR, TN, COB>(run_s, run_q, &sred[0][0][0], wave / WAVES_N, wn0, lane);
-        __syncthreads();
-        if (tid < COB) {
-            double a = 0.0, q = 0.0;
-#pragma unroll
-            for (int w = 0; w < WAVES_M; ++w) {
-                a += sred[w][0][tid];
-                q += sred[w][1][tid];
-            }
-            const int shard = (int)(blockIdx.x % (unsigned)ep.acc.shards);
-            xacc_add_shard(ep.acc, shard, n0 + tid, a);
-            xacc_add_shard(ep.acc, shard, CO + n0 + tid, q);
-        }
-    }
-}
-
-// ---- sub-pixel (stride-2 transposed 3x3) conv over LDS halo tiles: Ci = 64,
-// Co = 32, low-res width 32, bf16 (the decoder's last sub-pixel layer and the encoder layer-2 data gradient).
-// A persistent block keeps the packed weights [32][9 x 64] in LDS and walks 128-pixel low-res tiles (4 rows);
-// each tile's 5 input rows (the 4 plus the next, and a zero column right of the image) are staged once, and all
-// 4 phases' taps (1 + 2 + 2 + 4) read their fragments from there.
-// Template: CI input channels, COB output channels per block (NSPL blocks per tile), WI low-res width, ROWS
-// low-res rows per tile (TP = ROWS * WI = 128 pixels), DB: double-buffered halo.  WI * CI / 8 == 256.
-// WPE: waves per SIMD the register allocation targets (2: two blocks per CU, with DB = false to fit the LDS)
-template <int CI, int COB, int NSPL, int WI, int ROWS, bool DB, class EP, bool TR = true, bool XIN = false, int WPE = 1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void subpixel_halo_kernel(const bf16* __restrict__ x, int Hi, int ntiles,
-                                                            const bf16* __restrict__ wp, EP ep, int M, BnIn xin) {
-    constexpr int HR = ROWS + 1, HC = WI + 1, PS = CI + 8, CPP = CI / 8, TP = ROWS * WI;
-    static_assert(WI * CPP == 256 && TP == 128 && (COB == 32 || COB == 16), "halo chunk map / wave tiling");
-    constexpr int KP = 9 * CI + 8;                        // weight row: fragment rows on distinct 16-byte slots
-    constexpr int HS = HR * HC * PS;
-    constexpr int TM = 2, TN = COB / 16, CO = NSPL * COB;  // 4 waves x (32 pixels x COB channels)
-    __shared__ __attribute__((aligned(16))) bf16 Bs[COB * KP];
-    __shared__ __attribute__((aligned(16))) bf16 Hs[(DB ? 2 : 1) * HS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm0 = wave * 32;
-    const int tpi = Hi / ROWS;                            // tiles per image
-    const int nh = blockIdx.x % NSPL, n0 = nh * COB;
-    const int bstep = gridDim.x / NSPL;
-    __shared__ float bsh[COB];  // this block's bias columns
-    if (tid < COB) bsh[tid] = n0 + tid < CO ? ep.colbias(n0 + tid) : 0.f;
-    for (int c = tid; c < COB * 9 * CPP; c += 256) {      // this block's weight rows
-        const int n = c / (9 * CPP), q = c - n * (9 * CPP);
-        *reinterpret_cast<uint4*>(&Bs[n * KP + q * 8]) =
-            *reinterpret_cast<const uint4*>(wp + (int64_t)(n0 + n) * 9 * CI + q * 8);
-    }
-    for (int c = tid; c < (DB ? 2 : 1) * HR * CPP; c += 256) {  // the pad column (c = WI) stays zero
-        const int bufr = c / CPP, q = c - bufr * CPP;
-        *reinterpret_cast<uint4*>(&Hs[(bufr / HR) * HS + ((bufr % HR) * HC + WI) * PS + q * 8]) = make_uint4(0, 0, 0, 0);
-    }
-    uint4 hr[HR];  // HR rows x 256 chunks / 256 threads
-    auto row_off = [&](int b, int ih) { return (((int64_t)b * Hi + ih) * WI + tid / CPP) * CI + (tid % CPP) * 8; };
-    auto load_rows = [&](uint4* h, int t) {
-        const int b = t / tpi, r0 = (t - b * tpi) * ROWS;
-#pragma unroll
-        for (int u = 0; u < HR; ++u) {
-            const int ih = r0 + u;
-            h[u] = *reinterpret_cast<const uint4*>(x + row_off(b, ih < Hi ? ih : Hi - 1));  // zeroed when staged
-        }
-    };
-    float pr[XIN ? 4 : 1][8];  // XIN: this thread's 8 channels' BatchNorm parameters
-    // XIN: the rows of tile t inside the image become activations; rows r0 .. r0 + ROWS - 1 are this tile's to write
-    auto xform_rows = [&](uint4* h, int t) {
-        if constexpr (XIN) {
-            const int b = t / tpi, r0 = (t - b * tpi) * ROWS;
-#pragma unroll
-            for (int u = 0; u < HR; ++u) {
-                const int ih = r0 + u;
-                if (ih >= Hi) continue;
-                h[u] = bn_in_apply(h[u], pr);
-                if (u < ROWS && nh == 0) *reinterpret_cast<uint4*>(xin.a_out + row_off(b, ih)) = h[u];
-            }
-        }
-    };
-    auto store_rows = [&](const uint4* h, int buf, int t) {
-        const bool bottom = (t % tpi) == tpi - 1;  // the tile's last row is the zero padding below the image
-#pragma unroll
-        for (int u = 0; u < HR; ++u)
-            *reinterpret_cast<uint4*>(&Hs[buf * HS + (u * HC + tid / CPP) * PS + (tid % CPP) * 8]) =
-                (u == HR - 1 && bottom) ? make_uint4(0, 0, 0, 0) : h[u];
-    };
-    int t = blockIdx.x / NSPL, buf = 0;
-    if (t < ntiles) load_rows(hr, t);  // in flight during the statistics prologue
-    if constexpr (XIN) {
-        __shared__ BnInLds<CI> bl;
-        bn_in_prologue<CI>(xin, bl);
-        const int c0 = (tid % CPP) * 8;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            pr[0][k] = bl.prm[c0 + k];
-            pr[1][k] = bl.prm[CI + c0 + k];
-            pr[2][k] = bl.prm[2 * CI + c0 + k];
-            pr[3][k] = bl.prm[3 * CI + c0 + k];
-        }
-    }
-    if (t < ntiles) {
-        xform_rows(hr, t);
-        store_rows(hr, 0, t);
-    }
-    __syncthreads();
-    const int g8 = (lane >> 4) * 8;
-    // statistics (kStatMode 1): per-lane column sums over all tiles and phases in registers, one block reduction
-    // at the end (conv_s2_halo_kernel; per phase it cost two barriers, eight per tile)
-    constexpr int NS = TR ? TN * 4 : TN;
-    double run_s[NS], run_q[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) run_s[j] = run_q[j] = 0.0;
-    __shared__ double sred[EP::kStatMode == 1 ? 4 : 1][2][COB];
-    for (; t < ntiles; t += bstep) {
-        const int tn = t + bstep;
-        uint4* cur = hr;
-        load_rows(cur, min(tn, ntiles - 1));  // unconditional: conv_s2_halo_kernel
-        const bf16* H = Hs + buf * HS;
-#pragma unroll
-        for (int ph = 0; ph < 4; ++ph) {
-            const int py = ph >> 1, px = ph & 1;
-            f32x4_t acc[TM][TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ty = 0; ty < 2; ++ty) {
-                if (ty == 1 && !py) continue;
-                const int kh = py ? (ty ? 2 : 0) : 1, dr = (py && ty == 0) ? 1 : 0;
-#pragma unroll
-                for (int tx = 0; tx < 2; ++tx) {
-                    if (tx == 1 && !px) continue;
-                    const int kw = px ? (tx ? 2 : 0) : 1, dc = (px && tx == 0) ? 1 : 0;
-#pragma unroll
-                    for (int kc = 0; kc < CI / 32; ++kc) {
-                        bf16x8_t af[TM], bfr[TN];
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) {
-                            const int m = wm0 + i * 16 + (lane & 15);
-                            af[i] = *reinterpret_cast<const bf16x8_t*>(
-                                &H[((m / WI + dr) * HC + m % WI + dc) * PS + kc * 32 + g8]);
-                        }
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            const int n = j * 16 + (lane & 15);
-                            bfr[j] = *reinterpret_cast<const bf16x8_t*>(&Bs[n * KP + (kh * 3 + kw) * CI + kc * 32 + g8]);
-                        }
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < TN; ++j)  // TR: operands swapped (epilogue_tile_t)
-                                acc[i][j] = mfma_bf16<TR>(af[i], bfr[j], acc[i][j]);
-                    }
-                }
-            }
-            HaloEp<EP> e;
-            static_cast<EP&>(e) = ep;
-            e.lb = bsh;
-            e.nbase = n0;
-            e.set_phase(ph);
-            double cs[TR ? TN * 4 : TN], cq[TR ? TN * 4 : TN];
-            if constexpr (TR)
-                epilogue_tile_t<TM, TN, HaloEp<EP>, true>(e, acc, t * TP + wm0, n0, lane, M, CO,
-                                                  *reinterpret_cast<double(*)[TN][4]>(cs),
-                                                  *reinterpret_cast<double(*)[TN][4]>(cq));
-            else
-                epilogue_tile<TM, TN>(e, acc, t * TP + wm0, n0, lane, M, CO, cs, cq);
-            if constexpr (EP::kStatMode == 1) {
-#pragma unroll
-                for (int j = 0; j < NS; ++j) {
-                    run_s[j] += cs[j];
-                    run_q[j] += cq[j];
-                }
-            }
-        }
-        if constexpr (DB) {
-            if (tn < ntiles) {
-                xform_rows(cur, tn);
-                store_rows(cur, buf ^ 1, tn);
-            }
-            __syncthreads();
-            buf ^= 1;
-        } else {
-            if (tn < ntiles) xform_rows(cur, tn);
-            __syncthreads();  // every wave is done with this tile's halo
-            if (tn < ntiles) store_rows(cur, 0, tn);
-            __syncthreads();
-        }
-    }
-    if constexpr (EP::kStatMode == 1) {
-        stats_to_lds<TR, TN, COB>(run_s, run_q, &sred[0][0][0], wave, 0, lane);
-        __syncthreads();
-        if (tid < COB) {
-            const double a = (sred[0][0][tid] + sred[1][0][tid]) + (sred[2][0][tid] + sred[3][0][tid]);
-            const double q = (sred[0][1][tid] + sred[1][1][tid]) + (sred[2][1][tid] + sred[3][1][tid]);
-            const int shard = (int)(blockIdx.x % (unsigned)ep.acc.shards);
-            xacc_add_shard(ep.acc, shard, n0 + tid, a);
-            xacc_add_shard(ep.acc, shard, CO + n0 + tid, q);
-        }
-    }
-}
-
 
 }  // namespace
 
 namespace ops {
 
-static BnIn bn_in_of(const BnInput* xi) {
-    BnIn b{};
-    if (!xi) return b;
-    b.acc = xi->acc; b.R = xi->R; b.mean = xi->mean; b.invstd = xi->invstd; b.rmean = xi->rmean; b.rvar = xi->rvar;
-    b.nbt = xi->nbt; b.momentum = xi->momentum; b.eps = xi->eps; b.gamma = xi->gamma; b.beta = xi->beta;
-    b.a_out = static_cast<bf16*>(xi->a_out);
-    return b;
-}
-static bool conv_halo_shape(int Ci, int Co, int Wi, int Hi, int& which) {
-    which = (Ci == 32 && Co == 64 && Wi == 64 && Hi % 8 == 0) ? 1 : (Ci == 64 && Co == 128 && Wi == 32 && Hi % 8 == 0) ? 2 : 0;
-    return which != 0;
-}
-static bool subpixel_halo_shape(int Ci, int Co, int Wi, int Hi, int& which) {
-    which = (Ci == 64 && Co == 32 && Wi == 32 && Hi % 4 == 0) ? 1 : (Ci == 128 && Co == 64 && Wi == 16 && Hi % 8 == 0) ? 2 : 0;
-    return which != 0;
-}
 template <typename T>
 bool conv_s2_takes_input_bn(int B, int Hi, int Wi, int Ci, int Co) {
     (void)B;
-    int w;
-    return std::is_same<T, bf16>::value && conv_halo_shape(Ci, Co, Wi, Hi, w);
+    return std::is_same<T, bf16>::value && halo_find(kConvHalo, Ci, Co, Wi, Hi);
 }
 template <typename T>
 bool subpixel_takes_input_bn(int B, int Hi, int Wi, int Ci, int Co) {
     (void)B;
-    int w;
-    return std::is_same<T, bf16>::value && subpixel_halo_shape(Ci, Co, Wi, Hi, w);
+    return std::is_same<T, bf16>::value && halo_find(kSubpixelHalo, Ci, Co, Wi, Hi);
 }
 
 template <typename T>
@@ -938,43 +545,7 @@ int conv_s2(hipStream_t s, const T* x, int B, int Hi, int Wi, int Ci, const T* w
         return dispatch_nt<T>(s, al, bl, ef, M, Co, K, 1, ws, nullptr);
     }
     if constexpr (std::is_same<T, bf16>::value) {
-        int which;
-        conv_halo_shape(Ci, Co, Wi, Hi, which);
-        // (CI, Co, Wi): (32, 64, 64) below; (64, 128, 32) two 64-channel halves per 64-pixel tile, one halo buffer
-        // (the weights take half the LDS)
-        auto run = [&](auto kern_plain, auto kern_stats, auto kern_xin, int tp, int nspl, int cap = 256) -> int {
-            const int ntiles = M / tp;  // whole output rows: tiles stay inside an image
-            const int grid = std::min(ntiles * nspl, cap);
-            HLMC_PROBE_BEGIN(s);
-            if (st && st->acc.on()) {
-                WithStats<StoreRM<T>> eps;
-                static_cast<StoreRM<T>&>(eps) = ep;
-                eps.acc = st->acc;
-                if (xin) kern_xin<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, eps, M, bn_in_of(xin));
-                else kern_stats<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, eps, M, BnIn{});
-                st->done = true;
-            } else {
-                if (st) st->done = false;
-                kern_plain<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, ep, M, BnIn{});
-            }
-            HLMC_PROBE_END(s);
-            HLMC_LAUNCHED();
-            return (int)HLMC_OK;
-        };
-        using StRM = WithStats<StoreRM<T>>;  // per-element epilogue (TR = false), see dispatch_nt
-        // (32, 64, 64): 2-row (64-pixel) tiles and one halo buffer: 64 KB (73 KB with the input BatchNorm) and 176
-        // VGPRs, two blocks per CU on a 512-block grid.  Measured in the step: forward with the input BatchNorm +
-        // statistics 49.6 -> 42.7 us, the decoder data gradient 32.2 -> 31.5 us (4-row tiles, double-buffered, one
-        // block per CU before); the same with 4-row tiles and two 32-channel blocks per tile (the halo read twice)
-        // lost (50 -> 55 us)
-        if (which == 1)
-            return run(conv_s2_halo_kernel<32, 64, 1, 32, 2, false, StoreRM<T>, false, false, 2>,
-                       conv_s2_halo_kernel<32, 64, 1, 32, 2, false, StRM, false, false, 2>,
-                       conv_s2_halo_kernel<32, 64, 1, 32, 2, false, StRM, false, true, 2>, 64, 1, 512);
-        if (which == 2)
-            return run(conv_s2_halo_kernel<64, 64, 2, 16, 4, false, StoreRM<T>, false>,
-                       conv_s2_halo_kernel<64, 64, 2, 16, 4, false, StRM, false>,
-                       conv_s2_halo_kernel<64, 64, 2, 16, 4, false, StRM, false, true>, 64, 2);
+        if (const auto* h = halo_find(kConvHalo, Ci, Co, Wi, Hi)) return halo_launch(s, *h, x, Hi, wp, ep, M, st, xin);
     }
     return dispatch_nt<T>(s, al, bl, ep, M, Co, K, 1, ws, st);
 }
@@ -1001,45 +572,7 @@ int subpixel(hipStream_t s, const T* x, int B, int Hi, int Wi, int Ci, const T* 
     probe::site(probe::kSubpixel, 2.0 * M * Co * 9.0 * Ci,
                 (double)sizeof(T) * ((double)M * Ci + 9.0 * Ci * Co + 4.0 * M * Co));
     if constexpr (std::is_same<T, bf16>::value) {
-        int which;
-        subpixel_halo_shape(Ci, Co, Wi, Hi, which);
-        // (nspl, cap): channel splits and grid cap of the statistics / input-BN launches; (nspl_p, cap_p): of the
-        // plain launch
-        auto run = [&](auto kern_plain, auto kern_stats, auto kern_xin, int nspl, int cap, int nspl_p, int cap_p) -> int {
-            const int ntiles = M / 128;  // 128 low-res pixels (whole rows) per tile, inside one image
-            HLMC_PROBE_BEGIN(s);
-            if (st && st->acc.on()) {
-                const int grid = std::min(ntiles * nspl, cap);
-                WithStats<StoreSubpixel<T>> eps;
-                static_cast<StoreSubpixel<T>&>(eps) = ep;
-                eps.acc = st->acc;
-                if (xin) kern_xin<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, eps, M, bn_in_of(xin));
-                else kern_stats<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, eps, M, BnIn{});
-                st->done = true;
-            } else {
-                if (st) st->done = false;
-                kern_plain<<<std::min(ntiles * nspl_p, cap_p), 256, 0, s>>>(x, Hi, ntiles, wp, ep, M, BnIn{});
-            }
-            HLMC_PROBE_END(s);
-            HLMC_LAUNCHED();
-            return (int)HLMC_OK;
-        };
-        using StSP = WithStats<StoreSubpixel<T>>;  // per-element epilogue (TR = false), see dispatch_nt
-        // Two blocks per CU where a block fits in half the LDS (<= 80 KB) and 256 VGPRs: one halo buffer (no
-        // double buffering: the co-resident block covers the extra barrier) and a 512-block grid.  Measured
-        // (3 alternating rounds): the 32 x 32 / Ci 64 -> Co 32 shape, all three launches, 129.3k vs 128.0k clips/s
-        // (forward 53 -> 46 us, data gradient 72 -> 56 us in the step); the 16 x 16 / Ci 128 -> Co 64 data
-        // gradient with 16 channels per block (four blocks per tile, 79 KB) 38 -> 33 us, while its statistics /
-        // input-BN forms need 90 KB (one block per CU) and lost 48 -> 68 us; the Ci 32 -> Co 64 conv with two
-        // 32-channel blocks per tile (the halo read twice) lost 50 -> 55 / 32 -> 36 us
-        if (which == 1)
-            return run(subpixel_halo_kernel<64, 32, 1, 32, 4, false, StoreSubpixel<T>, false, false, 2>,
-                       subpixel_halo_kernel<64, 32, 1, 32, 4, false, StSP, false, false, 2>,
-                       subpixel_halo_kernel<64, 32, 1, 32, 4, false, StSP, false, true, 2>, 1, 512, 1, 512);
-        if (which == 2)
-            return run(subpixel_halo_kernel<128, 16, 4, 16, 8, false, StoreSubpixel<T>, false, false, 2>,
-                       subpixel_halo_kernel<128, 32, 2, 16, 8, false, StSP, false>,
-                       subpixel_halo_kernel<128, 32, 2, 16, 8, false, StSP, false, true>, 2, 256, 4, 512);
+        if (const auto* h = halo_find(kSubpixelHalo, Ci, Co, Wi, Hi)) return halo_launch(s, *h, x, Hi, wp, ep, M, st, xin);
     }
     return dispatch_nt<T>(s, al, bl, ep, M, Co, 4 * Ci, 4, ws, st);
 }

@@ -155,16 +155,7 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(XAcc acc, int C, int64_
     // xacc_column masks the sticky non-finite flag (common.hpp kXAccBad): a diverged column comes out NaN
     const double s = xacc_column(acc, c), q = xacc_column(acc, C + c);
     if (c == 0 && nbt) nbt[0] += 1;
-    const double m = s / (double)R;
-    double var = q / (double)R - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) {
-        const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
-        rmean[c] = (float)((1.0 - momentum) * rmean[c] + momentum * m);
-        rvar[c] = (float)((1.0 - momentum) * rvar[c] + momentum * unb);
-    }
+    bn_train_finalize(s, q, R, eps, momentum, mean[c], invstd[c], rmean ? rmean + c : nullptr, rmean ? rvar + c : nullptr);
 }
 
 __global__ void bn_eval_kernel(const float* rmean, const float* rvar, int C, float eps, float* mean, float* invstd) {
@@ -180,56 +171,24 @@ __global__ void bn_eval_kernel(const float* rmean, const float* rvar, int C, flo
 // Every block computes the same values; block 0 also stores the ones later kernels read (mean / invstd and the
 // running statistics; dgamma / dbeta).
 constexpr int kFinMaxC = 512;  // channels a consumer finalizes itself (LDS: 2 x 512 floats + 2 x 512 doubles)
-struct BnFin {
-    XAcc acc;                      // 2C columns
-    int64_t R = 0;                 // rows of the normalised map (forward)
-    float *mean = nullptr, *invstd = nullptr, *rmean = nullptr, *rvar = nullptr;  // forward outputs (block 0)
-    int64_t* nbt = nullptr;
-    float momentum = 0.f, eps = 0.f;
-    float *dgamma = nullptr, *dbeta = nullptr;  // backward outputs (block 0)
+struct BnFin : BnTrainFwd {                    // forward: acc, R and the outputs block 0 stores (common.hpp)
+    float *dgamma = nullptr, *dbeta = nullptr;  // backward outputs (block 0); acc: sum dz | sum dz*xhat
 };
-// The per-channel values from the totals tot (LDS, 2C doubles): fwd mean / invstd, bwd sum dz / sum dz*xhat
-template <bool kFwd>
-__device__ __forceinline__ void bn_fin_values(const BnFin& f, const double* tot, int C, int c, float& x0, float& x1,
-                                              double* var_out = nullptr) {
-    const double s = tot[c], q = tot[C + c];
-    if constexpr (kFwd) {
-        const double m = s / (double)f.R;
-        double var = q / (double)f.R - m * m;
-        if (var < 0.0) var = 0.0;
-        x0 = (float)m;
-        x1 = (float)(1.0 / sqrt(var + (double)f.eps));
-        if (var_out) *var_out = var;
-    } else {
-        x0 = (float)s;
-        x1 = (float)q;
-    }
-}
 // x0[c] / x1[c] (LDS floats, c < C) <- the per-channel values from the accumulator's totals (tot: LDS >= 2C
-// doubles; red: LDS >= 3 * 256 int64, may not overlap tot); block 0 stores the finalized per-channel outputs.
-// Ends with a barrier.
+// doubles; red: LDS >= 3 * 256 int64, may not overlap tot): fwd mean / invstd (bn_train_channel), bwd sum dz /
+// sum dz*xhat; block 0 stores the finalized per-channel outputs.  Ends with a barrier.
 template <bool kFwd>
 __device__ __forceinline__ void bn_fin_prologue(const BnFin& f, int C, double* tot, long long* red, float* x0s,
                                                 float* x1s) {
     xacc_fold(f.acc, tot, red);
     for (int c = threadIdx.x; c < C; c += kThreads) {
-        float x0, x1;
-        double var = 0.0;
-        bn_fin_values<kFwd>(f, tot, C, c, x0, x1, &var);
-        x0s[c] = x0;
-        x1s[c] = x1;
-        if (blockIdx.x == 0) {
-            if constexpr (kFwd) {
-                f.mean[c] = x0;
-                f.invstd[c] = x1;
-                if (f.rmean) {
-                    const double m = tot[c] / (double)f.R;
-                    const double unb = f.R > 1 ? var * (double)f.R / (double)(f.R - 1) : var;
-                    f.rmean[c] = (float)((1.0 - f.momentum) * f.rmean[c] + f.momentum * m);
-                    f.rvar[c] = (float)((1.0 - f.momentum) * f.rvar[c] + f.momentum * unb);
-                }
-                if (c == 0 && f.nbt) f.nbt[0] += 1;
-            } else {
+        if constexpr (kFwd) {
+            bn_train_channel(f, c, tot[c], tot[C + c], x0s[c], x1s[c]);
+        } else {
+            const float x0 = (float)tot[c], x1 = (float)tot[C + c];
+            x0s[c] = x0;
+            x1s[c] = x1;
+            if (blockIdx.x == 0) {
                 f.dbeta[c] = x0;
                 f.dgamma[c] = x1;
             }

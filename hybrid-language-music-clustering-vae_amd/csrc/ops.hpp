@@ -34,14 +34,9 @@ struct BnBwdFuse {
 // then the layer-below pre-BN map y, acc its statistics (2 Ci columns, delivered by its producer); the kernel
 // writes mean / invstd / running statistics like bn_act_train and the activation a_out (Ci channels, x's layout)
 // for the weight gradient that reads it.  Only where *_takes_input_bn says so (bf16 halo shapes, train mode).
-struct BnInput {
-    XAcc acc;
-    int64_t R;
-    float *mean, *invstd, *rmean, *rvar;
-    int64_t* nbt;
-    float momentum, eps;
-    const float *gamma, *beta;
-    void* a_out;
+struct BnInput : BnTrainFwd {  // the kernel argument itself (halo.hpp halo_kernel)
+    const float *gamma = nullptr, *beta = nullptr;
+    void* a_out = nullptr;  // T* of the launch
 };
 template <typename T>
 bool conv_s2_takes_input_bn(int B, int Hi, int Wi, int Ci, int Co);

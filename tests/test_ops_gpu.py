@@ -402,20 +402,68 @@ def test_device_randn_matches_philox_restatement(cuda):
 HALO = [(0, 64, 64, 32, 64), (0, 32, 32, 64, 128), (1, 32, 32, 64, 32), (1, 16, 16, 128, 64)]
 
 
+# Edge shapes of the same four layers (B, Hi): the persistent tile walk where it is not a whole number of equal passes.
+#   minimal: B = 1 at the smallest legal height: fewer tiles than the grid cap (grid = tiles x channel splits), the
+#     prefetch clamped on the block's only tile; the three one-tile shapes' tile is both first and last of its image
+#     (zero row above / below, a_out ownership);
+#   uneven: two tiles per image and two more tiles than a channel split has blocks (514 / 512, 130 / 128): two blocks
+#     walk two tiles, the rest one.
+HALO_EDGE = [(0, 1, 8, 64, 32, 64), (0, 1, 8, 32, 64, 128), (1, 1, 4, 32, 64, 32), (1, 1, 8, 16, 128, 64),
+             (0, 257, 8, 64, 32, 64), (0, 65, 16, 32, 64, 128), (1, 257, 8, 32, 64, 32), (1, 65, 16, 16, 128, 64)]
+
+
+def _halo_operands(g, kind, B, Hi, Wi, Ci, Co):
+    """Pre-BN input, torch-layout weight, packed weight, output shape of a halo-shape conv_s2 (0) / subpixel (1)."""
+    shift, scale = torch.randn(Ci, generator=g) * 0.5, torch.rand(Ci, generator=g) + 0.5
+    yin = (torch.randn(B, Hi, Wi, Ci, generator=g) * scale + shift).to(torch.bfloat16)
+    if kind == 0:
+        w = (torch.randn(Co, Ci, 3, 3, generator=g) / (3 * Ci ** 0.5)).to(torch.bfloat16)
+        return yin, w, w.permute(0, 2, 3, 1).contiguous(), (B, Hi // 2, Wi // 2, Co)
+    w = (torch.randn(Ci, Co, 3, 3, generator=g) / (3 * Ci ** 0.5)).to(torch.bfloat16)
+    return yin, w, w.permute(1, 2, 3, 0).contiguous(), (B, 2 * Hi, 2 * Wi, Co)
+
+
+def _halo_reference(kind, inp, w, b):
+    x = inp.float().permute(0, 3, 1, 2)
+    if kind == 0:
+        ref = F.conv2d(x, w.float(), b, stride=2, padding=1)
+    else:
+        ref = F.conv_transpose2d(x, w.float(), b, stride=2, padding=1, output_padding=1)
+    return ref.permute(0, 2, 3, 1)
+
+
 @pytest.mark.parametrize("bn_in", [False, True], ids=["stats", "bn_in+stats"])
 @pytest.mark.parametrize("kind,Hi,Wi,Ci,Co", HALO)
 def test_halo_fwd_bn_stats_bench_shapes(cuda, kind, Hi, Wi, Ci, Co, bn_in):
+    _halo_fwd_case(cuda, kind, BB, Hi, Wi, Ci, Co, bn_in)
+
+
+@pytest.mark.parametrize("bn_in", [False, True], ids=["stats", "bn_in+stats"])
+@pytest.mark.parametrize("kind,B,Hi,Wi,Ci,Co", HALO_EDGE)
+def test_halo_fwd_bn_stats_edge_shapes(cuda, kind, B, Hi, Wi, Ci, Co, bn_in):
+    _halo_fwd_case(cuda, kind, B, Hi, Wi, Ci, Co, bn_in)
+
+
+@pytest.mark.parametrize("kind,B,Hi,Wi,Ci,Co", HALO_EDGE)
+def test_halo_plain_edge_shapes(cuda, ws, kind, B, Hi, Wi, Ci, Co):
+    """The plain form of the halo kernels (no statistics: hlmc_op_conv_s2 / hlmc_op_subpixel, bf16) at the edge shapes
+    vs the CPU float32 conv of the bf16 operands: rel L2 < 3e-3 (test_conv_s2_bench_shapes_bf16's bound)."""
+    g = torch.Generator().manual_seed(kind * 100 + Hi + Ci + B)
+    x, w, wp, oshape = _halo_operands(g, kind, B, Hi, Wi, Ci, Co)
+    b = torch.randn(Co, generator=g) * 0.1
+    xd, wd, bd = x.to(cuda).contiguous(), wp.to(cuda), b.to(cuda)
+    y = torch.empty(*oshape, dtype=torch.bfloat16, device=cuda)
+    op = L.lib().hlmc_op_conv_s2 if kind == 0 else L.lib().hlmc_op_subpixel
+    L.check(op(L.stream(), L.HLMC_BF16, xd.data_ptr(), B, Hi, Wi, Ci, wd.data_ptr(), bd.data_ptr(), Co, y.data_ptr(),
+               ws.data_ptr(), WS_BYTES))
+    e = rel(y, _halo_reference(kind, x, w, b))
+    print(f"halo plain kind {kind} B={B} {Hi}x{Wi} {Ci}->{Co}: rel L2 {e:.2e}")
+    assert e < 3e-3
+
+
+def _halo_fwd_case(cuda, kind, B, Hi, Wi, Ci, Co, bn_in):
     g = torch.Generator().manual_seed(kind * 100 + Hi + Ci + int(bn_in))
-    shift, scale = torch.randn(Ci, generator=g) * 0.5, torch.rand(Ci, generator=g) + 0.5
-    yin = (torch.randn(BB, Hi, Wi, Ci, generator=g) * scale + shift).to(torch.bfloat16)
-    if kind == 0:
-        w = (torch.randn(Co, Ci, 3, 3, generator=g) / (3 * Ci ** 0.5)).to(torch.bfloat16)
-        wp = w.permute(0, 2, 3, 1).contiguous()
-        oshape = (BB, Hi // 2, Wi // 2, Co)
-    else:
-        w = (torch.randn(Ci, Co, 3, 3, generator=g) / (3 * Ci ** 0.5)).to(torch.bfloat16)
-        wp = w.permute(1, 2, 3, 0).contiguous()
-        oshape = (BB, 2 * Hi, 2 * Wi, Co)
+    yin, w, wp, oshape = _halo_operands(g, kind, B, Hi, Wi, Ci, Co)
     b = torch.randn(Co, generator=g) * 0.1
     gamma, beta = 1 + 0.1 * torch.randn(Ci, generator=g), 0.1 * torch.randn(Ci, generator=g)
     rm0, rv0 = 0.1 * torch.randn(Ci, generator=g), 1 + 0.1 * torch.rand(Ci, generator=g)
@@ -423,13 +471,13 @@ def test_halo_fwd_bn_stats_bench_shapes(cuda, kind, Hi, Wi, Ci, Co, bn_in):
                                                      rv=rv0.clone()).items()}
     nbt = torch.zeros(1, dtype=torch.int64, device=cuda)
     mean_o, inv_o = torch.empty(Ci, device=cuda), torch.empty(Ci, device=cuda)
-    a_out = torch.empty(BB, Hi, Wi, Ci, dtype=torch.bfloat16, device=cuda)
+    a_out = torch.empty(B, Hi, Wi, Ci, dtype=torch.bfloat16, device=cuda)
     y = torch.empty(*oshape, dtype=torch.bfloat16, device=cuda)
     sums = torch.empty(2 * Co, dtype=torch.float64, device=cuda)
     wsb = int(L.lib().hlmc_op_halo_workspace(Ci, Co))
     hws = torch.empty(wsb, dtype=torch.uint8, device=cuda)
     P = L.ptr
-    L.check(L.lib().hlmc_op_halo_fwd(L.stream(), kind, P(d["yin"]), BB, Hi, Wi, Ci, P(d["wp"]), P(d["b"]), Co, P(y),
+    L.check(L.lib().hlmc_op_halo_fwd(L.stream(), kind, P(d["yin"]), B, Hi, Wi, Ci, P(d["wp"]), P(d["b"]), Co, P(y),
                                      P(sums), P(d["gamma"]) if bn_in else None, P(d["beta"]) if bn_in else None,
                                      P(d["rm"]), P(d["rv"]), P(nbt), 0.1, 1e-5, P(mean_o), P(inv_o), P(a_out),
                                      P(hws), wsb), "hlmc_op_halo_fwd")
@@ -452,25 +500,19 @@ def test_halo_fwd_bn_stats_bench_shapes(cuda, kind, Hi, Wi, Ci, Co, bn_in):
         diff = (got.float() - a_ref.float()).abs()
         ulp = a_ref.float().abs().clamp_min(1e-30) * 2.0 ** -7
         frac_off = float((diff > 0).float().mean())
-        print(f"halo bn_in {Hi}x{Wi} {Ci}->{Co}: mean {e_mean:.1e} invstd {e_inv:.1e}, a_out off-by-ulp {frac_off:.1e}")
+        print(f"halo bn_in B={B} {Hi}x{Wi} {Ci}->{Co}: mean {e_mean:.1e} invstd {e_inv:.1e}, a_out off-by-ulp {frac_off:.1e}")
         assert bool((diff <= ulp).all()) and frac_off <= 1e-3
         inp = got
     else:
         assert torch.equal(d["rm"].cpu(), rm0) and int(nbt.item()) == 0   # untouched without gamma
-    x = inp.float().permute(0, 3, 1, 2)
-    if kind == 0:
-        ref = F.conv2d(x, w.float(), b, stride=2, padding=1)
-    else:
-        ref = F.conv_transpose2d(x, w.float(), b, stride=2, padding=1, output_padding=1)
-    ref = ref.permute(0, 2, 3, 1)
-    e = rel(y, ref)
+    e = rel(y, _halo_reference(kind, inp, w, b))
     yo = y.cpu().double().reshape(-1, Co)
     s_ref = torch.cat([yo.sum(0), (yo * yo).sum(0)])
     e_s = float(((sums.cpu() - s_ref).abs() / s_ref.abs().clamp_min(1e-300)).max())
     # the first moment can cancel: bound it by the sum of |y| instead
     e_s1 = float(((sums.cpu()[:Co] - s_ref[:Co]).abs() / yo.abs().sum(0)).max())
     e_s2 = float(((sums.cpu()[Co:] - s_ref[Co:]).abs() / s_ref[Co:]).max())
-    print(f"halo kind {kind} {Hi}x{Wi} {Ci}->{Co} bn_in={bn_in}: rel L2 {e:.2e}, stats {e_s1:.1e} / {e_s2:.1e}")
+    print(f"halo kind {kind} B={B} {Hi}x{Wi} {Ci}->{Co} bn_in={bn_in}: rel L2 {e:.2e}, stats {e_s1:.1e} / {e_s2:.1e}")
     assert e < 3e-3 and e_s1 < 1e-9 and e_s2 < 1e-9
 
 
