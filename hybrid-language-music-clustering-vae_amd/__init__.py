@@ -8,6 +8,7 @@ Drop-in surface (reference names):
                                                (librosa / sklearn calls of src/1_preprocessing*.py)
   KMeans                                       (sklearn KMeans calls of the three model scripts)
   DBSCAN, dbscan_eps_sweep                     (sklearn DBSCAN and the eps search of src/Convolutional_VAE.py)
+  AgglomerativeClustering, agglomerative_k_sweep   (sklearn's Ward clustering and its k sweep, same script)
   metrics.silhouette_score / davies_bouldin_score / calinski_harabasz_score / adjusted_rand_score /
   normalized_mutual_info_score / calculate_purity   (the sklearn.metrics evaluation calls)
   Adam                                         (torch.optim.Adam of the train loops)
@@ -17,7 +18,7 @@ Drop-in surface (reference names):
 All compute runs in libhlmc.so (hand-written HIP for gfx950); see include/hlmc.h.
 """
 from . import _lib
-from .cluster import DBSCAN, KMeans, dbscan_eps_sweep
+from .cluster import DBSCAN, AgglomerativeClustering, KMeans, agglomerative_k_sweep, dbscan_eps_sweep
 from .features import (SPECTRAL_FEATURES, StandardScaler, chroma_stft, extract_mel_spectrogram, extract_spectral_features,
                        mean_std_pool, mel_filterbank, melspectrogram, mfcc, power_to_db, rms, spectral_bandwidth,
                        spectral_centroid, spectral_rolloff, spectral_stats, zero_crossing_rate)
@@ -31,4 +32,5 @@ from . import pipeline
 
 __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_function", "vae_loss", "melspectrogram",
            "power_to_db", "mfcc", "extract_mel_spectrogram", "mean_std_pool", "mel_filterbank", "StandardScaler",
-           "KMeans", "DBSCAN", "dbscan_eps_sweep", "Adam", "Trainer", "GraphedStep", "metrics"]
+           "KMeans", "DBSCAN", "dbscan_eps_sweep", "AgglomerativeClustering", "agglomerative_k_sweep",
+           "Adam", "Trainer", "GraphedStep", "metrics"]

@@ -108,6 +108,9 @@ _SIGS = {
     "hlmc_dbscan_workspace": (c_i64, [c_i64, c_int]),
     "hlmc_dbscan_neighbors": (c_int, [c_vp, c_vp, c_i64, c_int, C.POINTER(c_f64), c_int, c_vp, c_vp, c_vp, c_i64]),
     "hlmc_dbscan_labels": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "hlmc_ward_workspace": (c_i64, [c_i64]),
+    "hlmc_ward_pdist": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
+    "hlmc_ward_chain": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
     "hlmc_op_conv_s2": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_op_subpixel": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_op_wgrad_s2": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_i64]),

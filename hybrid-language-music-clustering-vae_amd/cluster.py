@@ -28,6 +28,10 @@ result is bit-identical for any world size.
 
 DBSCAN (end of this file) replaces ``sklearn.cluster.DBSCAN(eps, min_samples=5).fit_predict`` and the eps search at
 src/Convolutional_VAE.py:347-374,382: fp64 MFMA neighbourhoods and union-find labelling on the device.
+
+AgglomerativeClustering (after DBSCAN) replaces ``sklearn.cluster.AgglomerativeClustering(n_clusters=k).fit_predict``
+and the k sweep at src/Convolutional_VAE.py:334-342,381: scipy's float64 distances and the nearest-neighbour chain with
+the Ward update on the device, sort / relabel / cut of the n - 1 merge records on the host.
 """
 from __future__ import annotations
 
@@ -516,3 +520,157 @@ def dbscan_eps_sweep(X, eps_range=np.arange(3.0, 20.0, 1.0), min_samples=5, *, d
     if best_sil == -1:
         best_eps = 10.0
     return best_eps, records
+
+
+# ====================================================================================== Ward agglomerative
+_WARD_MAX_N = 32768
+
+
+def _ward_device_x(X, device):
+    Xd = _dbscan_device_x(X, device)
+    if not bool(torch.isfinite(Xd).all()):
+        raise ValueError("Input X contains NaN or infinity.")
+    n = Xd.shape[0]
+    if n < 2:
+        raise ValueError(f"Found array with {n} sample(s) while a minimum of 2 is required by AgglomerativeClustering.")
+    if n > _WARD_MAX_N:
+        raise ValueError(f"AgglomerativeClustering: n_samples={n} is above the supported {_WARD_MAX_N} (the float64 "
+                         f"distance matrix takes n^2 * 8 bytes)")
+    return Xd
+
+
+def _ward_tree(Xd):
+    """The Ward tree of the float32 rows: (children int64 [n-1][2], distances float64 [n-1]), sklearn's ``children_``
+    and ``distances_`` bit for bit.  Device: the float64 distance matrix and the nearest-neighbour chain (n - 1 raw
+    merges).  Host, O(n log n) on the merge records: stable sort by height, union-find relabelling (row i creates
+    cluster n + i, each row is (min, max))."""
+    lib = L.lib()
+    n, d = Xd.shape
+    dev = Xd.device
+    ws_bytes = int(lib.hlmc_ward_workspace(n))
+    if ws_bytes <= 0:
+        raise ValueError(f"AgglomerativeClustering: n_samples={n} is outside the supported range [2, {_WARD_MAX_N}]")
+    with torch.cuda.device(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)   # the distance matrix is its first n * n * 8 bytes
+        ab = torch.empty(3, n - 1, dtype=torch.int32, device=dev)   # merge_a, merge_b, merge_size
+        md = torch.empty(n - 1, dtype=torch.float64, device=dev)
+        L.check(lib.hlmc_ward_pdist(L.stream(), Xd.data_ptr(), n, d, ws.data_ptr()), "hlmc_ward_pdist")
+        L.check(lib.hlmc_ward_chain(L.stream(), n, ws.data_ptr(), ab[0].data_ptr(), ab[1].data_ptr(), md.data_ptr(),
+                                    ab[2].data_ptr(), ws.data_ptr(), ws_bytes), "hlmc_ward_chain")
+        ab_h = ab.cpu().numpy()
+        md_h = md.cpu().numpy()
+    return _ward_relabel(ab_h[0], ab_h[1], md_h, n)
+
+
+def _ward_relabel(ma, mb, md, n):
+    order = np.argsort(md, kind="mergesort")
+    parent = list(range(2 * n - 1))
+    children = np.empty((n - 1, 2), dtype=np.int64)
+    ma, mb = ma.tolist(), mb.tolist()
+    for row, m in enumerate(order.tolist()):
+        pair = []
+        for x in (ma[m], mb[m]):
+            r = x
+            while parent[r] != r:
+                r = parent[r]
+            while parent[x] != r:        # path compression
+                parent[x], x = r, parent[x]
+            pair.append(r)
+        a, b = pair
+        children[row, 0], children[row, 1] = (a, b) if a < b else (b, a)
+        parent[a] = parent[b] = n + row
+    return children, md[order]
+
+
+def _ward_cut(children, n, n_clusters):
+    """sklearn's _hc_cut: a max-heap of node ids (heapq on negated ids) from the root, n_clusters - 1 rounds of push
+    then pushpop; label i goes to the leaves under heap[i] in heap-array order."""
+    import heapq
+    ch = children.tolist()
+    nodes = [-(max(ch[-1]) + 1)]
+    for _ in range(n_clusters - 1):
+        a, b = ch[-nodes[0] - n]
+        heapq.heappush(nodes, -a)
+        heapq.heappushpop(nodes, -b)
+    labels = np.zeros(n, dtype=np.int64)
+    for i, node in enumerate(nodes):
+        stack, leaves = [-node], []
+        while stack:
+            v = stack.pop()
+            if v < n:
+                leaves.append(v)
+            else:
+                stack.extend(ch[v - n])
+        labels[leaves] = i
+    return labels
+
+
+class AgglomerativeClustering:
+    """sklearn.cluster.AgglomerativeClustering with its defaults (Ward linkage, Euclidean metric, no connectivity)
+    for float32 data, the tree built on the GPU (src/Convolutional_VAE.py:334-342,381:
+    ``AgglomerativeClustering(n_clusters=k).fit_predict(latent_matrix)``).
+
+    ``labels_``, ``children_`` and ``distances_`` are bit-identical to sklearn 1.7.2 (scipy 1.15
+    ``hierarchy.ward``): float64 distances with scipy's pdist rounding, the nearest-neighbour chain with the
+    Lance-Williams Ward update in one single-workgroup launch, then on the host a stable sort by height, the
+    union-find relabelling and sklearn's heap cut.
+
+    The float64 distance matrix takes n^2 * 8 bytes (sklearn needs the same), so 2 <= n_samples <= 32768 (8 GiB);
+    the 100,000-row shape the K-Means and DBSCAN extras cover is out of scope here.  ``connectivity`` and
+    ``distance_threshold`` are not implemented.
+    """
+
+    def __init__(self, n_clusters=2, *, metric="euclidean", linkage="ward", compute_distances=False, device=None,
+                 connectivity=None, distance_threshold=None):
+        if linkage != "ward":
+            raise ValueError("only linkage='ward' (sklearn's default, the reference's) is implemented")
+        if metric != "euclidean":
+            raise ValueError("only metric='euclidean' (the only one Ward linkage accepts) is implemented")
+        if connectivity is not None or distance_threshold is not None:
+            raise ValueError("connectivity and distance_threshold are not implemented (the reference passes neither)")
+        self.n_clusters, self.metric, self.linkage = n_clusters, metric, linkage
+        self.compute_distances, self.device = compute_distances, device
+
+    def fit(self, X, y=None):
+        Xd = _ward_device_x(X, self.device)
+        n, d = Xd.shape
+        k = int(self.n_clusters)
+        if not 1 <= k <= n:
+            raise ValueError(f"n_clusters={self.n_clusters} must be in [1, n_samples={n}]")
+        self.children_, distances = _ward_tree(Xd)
+        if self.compute_distances:
+            self.distances_ = distances
+        self.n_clusters_ = k
+        self.n_leaves_ = n
+        self.n_connected_components_ = 1
+        self.n_features_in_ = d
+        self.labels_ = _ward_cut(self.children_, n, k)
+        return self
+
+    def fit_predict(self, X, y=None):
+        return self.fit(X).labels_
+
+
+def agglomerative_k_sweep(X, k_range=range(2, 15), *, device=None):
+    """The reference's agglomerative sweep (src/Convolutional_VAE.py:334-342): the reference refits the same Ward
+    tree for every k; here one tree is built and cut once per k.
+
+    Returns ``(best_k, records)``.  ``records[i]`` describes ``k_range[i]``: ``k``, ``labels`` (int64, identical to
+    ``AgglomerativeClustering(k).fit_predict(X)``) and ``silhouette`` (``metrics.silhouette_score(X, labels)``).
+    ``best_k`` follows the reference's rule: start at (2, -1) and replace on a strictly greater silhouette."""
+    from . import metrics as M
+    Xd = _ward_device_x(X, device)
+    n = Xd.shape[0]
+    ks = [int(k) for k in k_range]
+    if any(not 2 <= k <= n - 1 for k in ks):
+        raise ValueError(f"every k must be in [2, n_samples - 1 = {n - 1}] (the silhouette is defined there only)")
+    children, _ = _ward_tree(Xd)
+    records = []
+    best_k, best_sil = 2, -1
+    for k in ks:
+        labels = _ward_cut(children, n, k)
+        sil = M.silhouette_score(Xd, labels)
+        if sil > best_sil:
+            best_sil, best_k = sil, k
+        records.append({"k": k, "labels": labels, "silhouette": sil})
+    return best_k, records

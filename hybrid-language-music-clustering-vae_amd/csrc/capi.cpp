@@ -457,6 +457,16 @@ int hlmc_dbscan_labels(void* stream, int64_t n, int E, int e, int min_samples, c
                           n_clusters);
 }
 
+// ------------------------------------------------------------------------------------ Ward
+int64_t hlmc_ward_workspace(int64_t n) { return (int64_t)ward::workspace(n); }
+int hlmc_ward_pdist(void* stream, const float* X, int64_t n, int d, double* D) {
+    return ward::pdist(S(stream), X, n, d, D);
+}
+int hlmc_ward_chain(void* stream, int64_t n, double* D, int32_t* merge_a, int32_t* merge_b, double* merge_dist,
+                    int32_t* merge_size, void* ws, int64_t ws_bytes) {
+    return ward::chain(S(stream), n, D, merge_a, merge_b, merge_dist, merge_size, ws, ws_bytes < 0 ? 0 : (size_t)ws_bytes);
+}
+
 // ------------------------------------------------------------------------------------ op-level entries
 // Individual GEMM-family kernels (the building blocks of hlmc_net_*), exposed for testing and reuse.
 #define DT_DISPATCH(dtype, CALL_F32, CALL_BF16) ((dtype) == HLMC_BF16 ? (CALL_BF16) : (CALL_F32))

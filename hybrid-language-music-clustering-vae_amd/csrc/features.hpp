@@ -101,4 +101,13 @@ int labels(hipStream_t s, int64_t n, int E, int e, int min_samples, const int32_
            int32_t* labels_out, uint8_t* core_out, int32_t* n_clusters);
 }  // namespace dbscan
 
+// Ward agglomerative clustering with sklearn's tree (ward.hip): the full float64 distance matrix in scipy's pdist
+// arithmetic, then the nearest-neighbour chain with the Lance-Williams update in one launch of one workgroup.
+namespace ward {
+size_t workspace(int64_t n);
+int pdist(hipStream_t s, const float* X, int64_t n, int d, double* D);
+int chain(hipStream_t s, int64_t n, double* D, int32_t* merge_a, int32_t* merge_b, double* merge_dist,
+          int32_t* merge_size, void* ws, size_t ws_bytes);
+}  // namespace ward
+
 }  // namespace hlmc

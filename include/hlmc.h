@@ -351,6 +351,33 @@ int hlmc_dbscan_neighbors(void* stream, const float* X, int64_t n, int d, const 
 int hlmc_dbscan_labels(void* stream, int64_t n, int E, int e, int min_samples, const int32_t* counts, void* ws,
                        int64_t ws_bytes, int32_t* labels, uint8_t* core, int32_t* n_clusters);
 
+/* ---- Ward agglomerative clustering --------------------------------------------------------------------------------
+ * sklearn.cluster.AgglomerativeClustering(n_clusters=k).fit_predict(latent_matrix) at src/Convolutional_VAE.py:334-342,
+ * 381 (Ward linkage, no connectivity = scipy.cluster.hierarchy.ward on the float64-upcast rows).  2 <= n <= 32768
+ * (the distance matrix is n * n * 8 bytes, 8 GiB at the cap), d >= 1.
+ *
+ * hlmc_ward_pdist: D [n][n] float64, full and symmetric with a zero diagonal, row-major.  D[i][j] = sqrt(s) with
+ * s = 0 and then, for k = 0 .. d-1 in that order, t = x_ik - x_jk, s = s + t * t in float64 without FMA: scipy's pdist
+ * bit for bit.  X [n][d] f32.
+ *
+ * hlmc_ward_chain: the nearest-neighbour chain on D (which it destroys), n - 1 merges, one launch of one workgroup.
+ * An empty chain starts at the lowest live index; from the chain top x the scan starts at the predecessor and takes
+ * a live i != x only when D[x][i] is strictly smaller (ties: the predecessor first, then the lowest index).  Merge m
+ * in merge order (NOT sorted by height): merge_a[m] < merge_b[m] the two representatives (a dies, b carries the
+ * merged cluster), merge_dist[m] their distance, merge_size[m] the merged point count; all four are device arrays of
+ * n - 1 elements.  Distances to the merged cluster follow Lance-Williams for Ward, left to right without FMA:
+ *   t = 1.0 / (double)(ni + nx + ny)
+ *   sqrt(((ni + nx) * t) * dxi * dxi + ((ni + ny) * t) * dyi * dyi - (ni * t) * dxy * dxy)
+ * Workspace (hlmc_ward_workspace bytes): [D: n * n * 8 rounded up to 256][int32 status, 256 bytes][int32 chain[n]].
+ * The size includes room for D so that one allocation serves both stages (pass D = ws); D may also live elsewhere.
+ * The status word is 0 after a complete run, 1 when a scan found no neighbour (NaN or +inf in D), 2 when a loop
+ * bound computed from n was exhausted; the kernel then stops, and the call returns HLMC_EDEVICE.  The call copies
+ * the status word back and so synchronises the stream: the merge records are complete when it returns. */
+int64_t hlmc_ward_workspace(int64_t n);            /* bytes incl. D; 0 when n is out of range */
+int hlmc_ward_pdist(void* stream, const float* X, int64_t n, int d, double* D);
+int hlmc_ward_chain(void* stream, int64_t n, double* D /* in, destroyed */, int32_t* merge_a, int32_t* merge_b,
+                    double* merge_dist, int32_t* merge_size, void* ws, int64_t ws_bytes);
+
 
 /* ============================================================== op-level entry points
  * The kernels hlmc_net_* is built from, on NHWC activations (dtype HLMC_F32 / HLMC_BF16 for x, y, packed
