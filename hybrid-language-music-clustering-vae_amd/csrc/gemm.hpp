@@ -462,6 +462,13 @@ struct WithStats : Base {
     static constexpr int kStatMode = 1;
     XAcc acc;
 };
+template <class EP>
+inline WithStats<EP> with_stats(const EP& ep, const XAcc& acc) {
+    WithStats<EP> eps;
+    static_cast<EP&>(eps) = ep;
+    eps.acc = acc;
+    return eps;
+}
 
 // Split-K partial slab: ws[((phase * S + split) * M + m) * N + n]
 struct StorePartial {
@@ -1002,61 +1009,71 @@ struct StorePartialZ : StorePartial {
     __device__ void set_split(int z) { split = z; }  // the block's (XCD-remapped) K-split index
 };
 
-// Reduce split-K partials (fixed order => deterministic) then apply the final epilogue.
-template <class EP>
-__global__ void splitk_reduce_kernel(const float* ws, EP ep, int M, int N, int S, int phases) {
-    int64_t total = (int64_t)phases * M * N;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int n = (int)(i % N);
-        int64_t t = i / N;
-        int m = (int)(t % M);
-        int ph = (int)(t / M);
-        const float* p = ws + ((int64_t)ph * S * M + m) * N + n;
-        const int64_t st = (int64_t)M * N;
-        // fixed summation order (k ascending) with 4 slab loads in flight
-        float s = 0.f;
-        int k = 0;
-        for (; k + 4 <= S; k += 4) {
-            const float a0 = p[k * st], a1 = p[(k + 1) * st], a2 = p[(k + 2) * st], a3 = p[(k + 3) * st];
-            s += a0; s += a1; s += a2; s += a3;
-        }
-        for (; k < S; ++k) s += p[k * st];
-        EP e = ep;
-        e.set_phase(ph);
-        e.store(e.row(m), n, s);
+// ---- the split-K slab sum, stated once for every reduce kernel below (the statistics reduce keeps its own loop).
+// A thread owns VW consecutive columns of one output row: a float (VW 1) or a float4 added component-wise (VW 4, 16-byte
+// slab loads), so an output's additions are the same, in the same order, at either width: the same bits.
+template <int VW>
+using slab_t = std::conditional_t<VW == 4, float4, float>;
+__device__ __forceinline__ void slab_add(float& a, float b) { a += b; }
+__device__ __forceinline__ void slab_add(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+__device__ __forceinline__ float slab_at(float v, int) { return v; }
+__device__ __forceinline__ float slab_at(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+// Slabs g, g + G, g + 2G, ... < S of p (slab stride st) in ascending order: four loads issued before their four adds,
+// then the tail one slab at a time.  G = 1, g = 0 is the plain split-order sum; fixed order => deterministic.
+template <int VW, int G, class I>
+__device__ __forceinline__ slab_t<VW> slab_sum(const float* __restrict__ p, I st, int S, int g) {
+    using V = slab_t<VW>;
+    auto ld = [&](int k) { return *reinterpret_cast<const V*>(p + k * st); };
+    V acc{};
+    int k = g;
+    for (; k + 3 * G < S; k += 4 * G) {
+        const V a0 = ld(k), a1 = ld(k + G), a2 = ld(k + 2 * G), a3 = ld(k + 3 * G);
+        slab_add(acc, a0); slab_add(acc, a1); slab_add(acc, a2); slab_add(acc, a3);
     }
+    for (; k < S; k += G) slab_add(acc, ld(k));
+    return acc;
+}
+// Columns n .. n + VW - 1 of row m (one row: N % VW == 0) through the final epilogue
+template <class EP>
+__device__ __forceinline__ void slab_store(const EP& ep, int ph, int m, int n, float v) {
+    EP e = ep;
+    e.set_phase(ph);
+    e.store(e.row(m), n, v);
+}
+template <class EP>
+__device__ __forceinline__ void slab_store(const EP& ep, int ph, int m, int n, const float4& v) {
+    EP e = ep;
+    e.set_phase(ph);
+    const auto rw = e.row(m);
+    e.store(rw, n, v.x);
+    e.store(rw, n + 1, v.y);
+    e.store(rw, n + 2, v.z);
+    e.store(rw, n + 3, v.w);
 }
 
-// The same with one float4 of outputs per thread (N % 4 == 0, phases * S * M * N < 2^31, 16-byte aligned slabs):
-// 16-byte slab loads and 32-bit index math (the 64-bit divisions above cost more than the loads); each output's
-// additions in the same order as above (the same bits)
-template <class EP>
-__global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __restrict__ ws, EP ep, int M, int N, int S,
-                                                             int phases, FastDiv dN, FastDiv dM) {
-    const uint32_t e = (blockIdx.x * 256u + threadIdx.x) * 4u;
-    if (e >= (uint32_t)phases * (uint32_t)M * (uint32_t)N) return;
-    const uint32_t t = dN.div(e), n = e - t * (uint32_t)N;
-    const uint32_t ph = dM.div(t), m = t - ph * (uint32_t)M;
-    const uint32_t st = (uint32_t)M * (uint32_t)N;
-    const float* p = ws + ((ph * (uint32_t)S) * (uint32_t)M + m) * (uint32_t)N + n;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto add = [](float4& x, const float4& y) { x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w; };
-    int k = 0;
-    for (; k + 4 <= S; k += 4) {
-        const float4 a0 = *reinterpret_cast<const float4*>(p + k * st);
-        const float4 a1 = *reinterpret_cast<const float4*>(p + (k + 1) * st);
-        const float4 a2 = *reinterpret_cast<const float4*>(p + (k + 2) * st);
-        const float4 a3 = *reinterpret_cast<const float4*>(p + (k + 3) * st);
-        add(a, a0); add(a, a1); add(a, a2); add(a, a3);
+// Reduce split-K partials then apply the final epilogue.  VW 1: any shape, a grid-stride loop with 64-bit index math.
+// VW 4 (N % 4 == 0, phases * S * M * N < 2^31, 16-byte aligned slabs): one float4 of outputs per thread and 32-bit
+// index math (the 64-bit divisions cost more than the loads).
+template <int VW, class EP>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, EP ep, int M, int N, int S,
+                                                            int phases, FastDiv dN, FastDiv dM) {
+    if constexpr (VW == 4) {
+        const uint32_t e = (blockIdx.x * 256u + threadIdx.x) * 4u;
+        if (e >= (uint32_t)phases * (uint32_t)M * (uint32_t)N) return;
+        const uint32_t t = dN.div(e), n = e - t * (uint32_t)N;
+        const uint32_t ph = dM.div(t), m = t - ph * (uint32_t)M;
+        const uint32_t st = (uint32_t)M * (uint32_t)N;
+        const float* p = ws + ((ph * (uint32_t)S) * (uint32_t)M + m) * (uint32_t)N + n;
+        slab_store(ep, (int)ph, (int)m, (int)n, slab_sum<4, 1>(p, st, S, 0));
+    } else {
+        const int64_t total = (int64_t)phases * M * N, st = (int64_t)M * N;
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+            const int n = (int)(i % N);
+            const int64_t t = i / N;
+            const int m = (int)(t % M), ph = (int)(t / M);
+            slab_store(ep, ph, m, n, slab_sum<1, 1>(ws + ((int64_t)ph * S * M + m) * N + n, st, S, 0));
+        }
     }
-    for (; k < S; ++k) add(a, *reinterpret_cast<const float4*>(p + k * st));
-    EP o = ep;
-    o.set_phase((int)ph);
-    const auto rw = o.row((int)m);
-    o.store(rw, (int)n, a.x);
-    o.store(rw, (int)n + 1, a.y);
-    o.store(rw, (int)n + 2, a.z);
-    o.store(rw, (int)n + 3, a.w);
 }
 
 // The same reduction for a launch whose output feeds a train-mode BatchNorm: block = a tile of 4 * RU output rows
@@ -1133,8 +1150,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* w
 // ============================================================================ TN (weight-gradient) loaders
 // Contract: Col prep(int col) (once per chunk column, outside the K loop); uint4 load(int k, const Col&)
 // returns V consecutive columns of k-row k.
+// Stepped form (gemm_tn_kernel) of a loader L with prep / vload / load: the chunk's row j of the K-step and its
+// column, the step's first row k0.  (An empty base: L's aggregate initialisers begin with {} for it.)
+template <class L>
+struct KRowStepped {
+    struct Pre {
+        typename L::Col cl;
+        int j;
+    };
+    __device__ Pre pre(int j, int m) const { return Pre{self().prep(m), j}; }
+    __device__ int step(int k0) const { return k0; }
+    template <bool VEC>
+    __device__ uint4 sload(int k0, const Pre& p) const {
+        return VEC ? self().vload(k0 + p.j, p.cl) : self().load(k0 + p.j, p.cl);
+    }
+
+private:
+    __device__ const L& self() const { return static_cast<const L&>(*this); }
+};
 template <typename T>
-struct KRowDense {
+struct KRowDense : KRowStepped<KRowDense<T>> {
     const T* p;
     int ld, Kd, Md;  // rows (k) and columns (m/n)
     bool vec;        // rows 16-byte aligned (ld % V == 0)
@@ -1172,21 +1207,13 @@ struct KRowDense {
         for (int i = 0; i < V; ++i)
             x.e[i] = (m + i < Md) ? r[m + i] : from_f32<T>((ones && m + i == Md) ? 1.f : 0.f);
         return x.u;
-    }    // stepped form (gemm_tn_kernel): the chunk's row j of the K-step and its column, the step's first row k0
-    struct Pre {
-        Col cl;
-        int j;
-    };
-    __device__ Pre pre(int j, int m) const { return Pre{prep(m), j}; }
-    __device__ int step(int k0) const { return k0; }
-    template <bool VEC>
-    __device__ uint4 sload(int k0, const Pre& p) const { return VEC ? vload(k0 + p.j, p.cl) : load(k0 + p.j, p.cl); }
+    }
 };
 
 // H loader for stride-2 conv / transposed conv weight gradient: k = (b, r, c) over the LOW-res grid,
 // n = (kh, kw, ci): H(k, n) = Xh[b, 2r-1+kh, 2c-1+kw, ci] over the HIGH-res NHWC map [B, 2Hl, 2Wl, C].
 template <typename T>
-struct KRowConvS2 {
+struct KRowConvS2 : KRowStepped<KRowConvS2<T>> {
     const T* x;
     int Hl, Wl, C, Kd;  // Kd = B*Hl*Wl
     FastDiv dW, dH;     // division by Wl and Hl
@@ -1205,35 +1232,34 @@ struct KRowConvS2 {
     // to divergent branches around the index math, and the joins cost the weight-gradient loop its exact wait counts:
     // it waited for every outstanding load at the LDS store of the oldest)
     __device__ const void* addr(int k, const Col& cl) const {
-        const uint32_t t = dW.div((uint32_t)k);
-        const int c = k - (int)t * Wl;
-        const uint32_t b = dH.div(t);
-        const int r = (int)t - (int)b * Hl;
-        const bool zero = k >= Kd || !cl.ok || (r == 0 && cl.kh == 0) || (c == 0 && cl.kw == 0);
-        const int64_t pix = ((int64_t)b * 2 * Hl + 2 * r - 1) * (2 * Wl) + 2 * c - 1;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(x + pix * C + cl.off);
-        return reinterpret_cast<const void*>(zero ? reinterpret_cast<uintptr_t>(&g_zero16) : a);
+        const Tap t = tap(k, cl);
+        return reinterpret_cast<const void*>(t.zero ? reinterpret_cast<uintptr_t>(&g_zero16)
+                                                    : reinterpret_cast<uintptr_t>(t.p));
     }
     __host__ bool vec_ok() const { return true; }
     __device__ uint4 vload(int k, const Col& cl) const { return *reinterpret_cast<const uint4*>(addr(k, cl)); }
     __device__ uint4 load(int k, const Col& cl) const {
         if (k >= Kd || !cl.ok) return make_uint4(0, 0, 0, 0);
+        const Tap t = tap(k, cl);
+        if (t.zero) return make_uint4(0, 0, 0, 0);
+        return *reinterpret_cast<const uint4*>(t.p);
+    }
+
+private:
+    // k = (b, r, c): the chunk's address at tap (kh, kw) of low-res pixel (r, c) of image b, and whether it is a zero
+    // chunk (a row past K, a column past N, the padding row / column)
+    struct Tap {
+        const T* p;
+        bool zero;
+    };
+    __device__ Tap tap(int k, const Col& cl) const {
         const uint32_t t = dW.div((uint32_t)k);
         const int c = k - (int)t * Wl;
         const uint32_t b = dH.div(t);
         const int r = (int)t - (int)b * Hl;
-        if ((r == 0 && cl.kh == 0) || (c == 0 && cl.kw == 0)) return make_uint4(0, 0, 0, 0);
         const int64_t pix = ((int64_t)b * 2 * Hl + 2 * r - 1) * (2 * Wl) + 2 * c - 1;
-        return *reinterpret_cast<const uint4*>(x + pix * C + cl.off);
-    }    // stepped form (gemm_tn_kernel): the chunk's row j of the K-step and its column, the step's first row k0
-    struct Pre {
-        Col cl;
-        int j;
-    };
-    __device__ Pre pre(int j, int m) const { return Pre{prep(m), j}; }
-    __device__ int step(int k0) const { return k0; }
-    template <bool VEC>
-    __device__ uint4 sload(int k0, const Pre& p) const { return VEC ? vload(k0 + p.j, p.cl) : load(k0 + p.j, p.cl); }
+        return Tap{x + pix * C + cl.off, k >= Kd || !cl.ok || (r == 0 && cl.kh == 0) || (c == 0 && cl.kw == 0)};
+    }
 };
 
 // Buffer-descriptor forms of the two weight-gradient loaders for power-of-two sizes (every layer of the model: image
@@ -1561,93 +1587,40 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN)) void gemm_tn_kernel(LL 
     TN_TS(3);
 }
 
-// Split-K reduction parallel over the splits as well as the outputs: a block holds 256 / G outputs x G split
-// groups; thread (group g, output o) adds the slabs s = g, g + G, ... (loads issued 4 at a time) in order, then
-// the G group sums are added in group order.  Fixed order => deterministic; G = 1 is the plain split-order sum.
-// Deep split counts (the 16-262k-row weight gradients split 50-170 ways over 3-18 tiles) are latency chains
-// otherwise: one thread per output walking S slabs waits S / 4 memory round trips.
 // an epilogue's optional side task (E::extra(), e.g. StoreWgradConv's bias gradient), run once per reduce launch
 template <class E>
 __device__ __forceinline__ auto ep_extra(const E& e, int) -> decltype(e.extra(), void()) { e.extra(); }
 template <class E>
 __device__ __forceinline__ void ep_extra(const E&, long) {}
 
-template <int G, class EP>
+// Split-K reduction parallel over the splits as well as the outputs: a block holds 256 / G threads x G split
+// groups; thread (group g, output o) adds the slabs s = g, g + G, ... (slab_sum) in order, then the G group sums
+// are added in group order.  Fixed order => deterministic; G = 1 is the plain split-order sum.
+// Deep split counts (the 16-262k-row weight gradients split 50-170 ways over 3-18 tiles) are latency chains
+// otherwise: one thread per output walking S slabs waits S / 4 memory round trips.
+// A thread holds VW consecutive outputs of one row (VW 4: N % 4 == 0, 16-byte aligned slabs: 16-byte slab loads, 4x
+// the bytes in flight per thread).
+template <int VW, int G, class EP>
 __global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(const float* __restrict__ ws, EP ep, int M, int N,
                                                                     int S) {
     ep_extra(ep, 0);
-    constexpr int OPB = 256 / G;
-    __shared__ float part[G][OPB];
+    constexpr int OPB = 256 / G;  // threads (outputs of VW columns) per group
+    __shared__ slab_t<VW> part[G][OPB];
     const int o = threadIdx.x % OPB, g = threadIdx.x / OPB;
-    const int64_t idx = (int64_t)blockIdx.x * OPB + o;
+    const int64_t idx = ((int64_t)blockIdx.x * OPB + o) * VW;
     const int64_t total = (int64_t)M * N;
-    const int64_t st = total;
-    float acc = 0.f;
-    if (idx < total) {
-        const float* p = ws + idx;
-        int k = g;
-        for (; k + 3 * G < S; k += 4 * G) {
-            const float a0 = p[k * st], a1 = p[(k + G) * st], a2 = p[(k + 2 * G) * st], a3 = p[(k + 3 * G) * st];
-            acc += a0; acc += a1; acc += a2; acc += a3;
-        }
-        for (; k < S; k += G) acc += p[k * st];
-    }
+    slab_t<VW> acc{};
+    if (idx < total) acc = slab_sum<VW, G>(ws + idx, total, S, g);
     if constexpr (G > 1) {
         part[g][o] = acc;
         __syncthreads();
         if (g != 0) return;
 #pragma unroll
-        for (int j = 1; j < G; ++j) acc += part[j][o];
+        for (int j = 1; j < G; ++j) slab_add(acc, part[j][o]);
     }
     if (idx < total) {
         const int m = (int)(idx / N), n = (int)(idx - (int64_t)m * N);
-        EP e = ep;
-        e.set_phase(0);
-        e.store(e.row(m), n, acc);
-    }
-}
-// The same with 4 consecutive outputs per thread (N % 4 == 0, 16-byte aligned slabs): 16-byte slab loads, 4x the
-// bytes in flight per thread; each output's additions in the same order as above (the same bits)
-template <int G, class EP>
-__global__ __launch_bounds__(256) void splitk_reduce_grouped4_kernel(const float* __restrict__ ws, EP ep, int M, int N,
-                                                                     int S) {
-    ep_extra(ep, 0);
-    constexpr int OPB = 256 / G;  // float4 outputs per block
-    __shared__ float4 part[G][OPB];
-    const int o = threadIdx.x % OPB, g = threadIdx.x / OPB;
-    const int64_t idx = ((int64_t)blockIdx.x * OPB + o) * 4;
-    const int64_t total = (int64_t)M * N;
-    const int64_t st = total;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto add = [](float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; };
-    if (idx < total) {
-        const float* p = ws + idx;
-        int k = g;
-        for (; k + 3 * G < S; k += 4 * G) {
-            const float4 a0 = *reinterpret_cast<const float4*>(p + k * st);
-            const float4 a1 = *reinterpret_cast<const float4*>(p + (k + G) * st);
-            const float4 a2 = *reinterpret_cast<const float4*>(p + (k + 2 * G) * st);
-            const float4 a3 = *reinterpret_cast<const float4*>(p + (k + 3 * G) * st);
-            add(acc, a0); add(acc, a1); add(acc, a2); add(acc, a3);
-        }
-        for (; k < S; k += G) add(acc, *reinterpret_cast<const float4*>(p + k * st));
-    }
-    if constexpr (G > 1) {
-        part[g][o] = acc;
-        __syncthreads();
-        if (g != 0) return;
-#pragma unroll
-        for (int j = 1; j < G; ++j) add(acc, part[j][o]);
-    }
-    if (idx < total) {
-        const int m = (int)(idx / N), n = (int)(idx - (int64_t)m * N);  // N % 4 == 0: the 4 outputs share row m
-        EP e = ep;
-        e.set_phase(0);
-        const auto rw = e.row(m);
-        e.store(rw, n, acc.x);
-        e.store(rw, n + 1, acc.y);
-        e.store(rw, n + 2, acc.z);
-        e.store(rw, n + 3, acc.w);
+        slab_store(ep, 0, m, n, acc);
     }
 }
 

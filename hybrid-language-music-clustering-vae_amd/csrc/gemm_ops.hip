@@ -12,7 +12,8 @@ namespace {
 
 // split-K grid targets (A/B on the bench step, scripts in DESIGN.md §8): NT (forward / data-gradient convs,
 // linears) 512: 101.8k vs 101.2k at 256 (round 2, after the small split-K grids moved to the LDS-DMA ring;
-// round 1 measured 256 ahead of 512 and 128); TN (weight gradients) 512: 93.2k vs 92.8k at 1024, 90.7k at 2048
+// round 1 measured 256 ahead of 512 and 128); TN (weight gradients) 192, twice that for K >= kTnLongK (round 1
+// measured 512: 93.2k vs 92.8k at 1024, 90.7k at 2048; the later rounds that brought it to 192 are at plan_tn)
 constexpr int kNtTargetBlocks = 512;
 constexpr int kTnTargetBlocks = 192;
 constexpr int kTnLongK = 131072;
@@ -21,9 +22,22 @@ constexpr int kTnKch8Min = 1024;
 // it helps the TN (weight-gradient) family and slows the sub-pixel / conv NT families by 10-20 %
 constexpr int kXcdRemapKinds = probe::kWgradS2 | probe::kLinearWgrad;
 
-// Split-K plan shared by the launcher and the workspace query (must agree).
+// Split-K plan: S splits of ksl reduction rows each.
 struct Plan {
     int S, ksl;
+};
+// A tile shape as a type.  Each family names its shapes in one place, with_nt_tile / with_linear_tile / with_tn_tile,
+// which calls f with the family's choice for a problem; a launch and its workspace query both go through it and
+// through the same nt_plan / tn_plan, so they cannot disagree.
+template <int BM_, int BN_, int WM_, int WN_>
+struct Tile {
+    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+};
+// The grid of a launch under one tile shape: M x N tiles (per phase), the split-K plan, the bytes of its fp32 slabs
+struct GemmPlan {
+    int tiles;
+    Plan pl;
+    size_t slab_bytes;
 };
 // BK = the largest K-step (split ranges are multiples of it); the minimum work per split is counted in
 // steps of the short (BK/2) K-step the kernel uses for short ranges
@@ -80,9 +94,10 @@ inline bool use_ploop(int phases, int tmn, int pipe) { return phases >= 2 && pip
 
 // TR: transposed accumulators + 4-column vector stores (epilogue_tile_t; needs N % 4 == 0 and 4-aligned row
 // strides: the conv / sub-pixel NHWC outputs and their split-K slabs), else the per-element epilogue (linears)
-template <typename T, int BM, int BN, int WM, int WN, bool TR, class AL, class BL, class E>
+template <typename T, class TL, bool TR, class AL, class BL, class E>
 void nt_kernel_launch_tr(hipStream_t s, dim3 grid, const AL& al, const BL& bl, const E& ep, int M, int N, int ksl,
                          bool long_k, int pipe) {
+    constexpr int BM = TL::BM, BN = TL::BN, WM = TL::WM, WN = TL::WN;
     const int rm = xcd_remap_for_site();
     const int ploop = use_ploop((int)grid.y, (int)grid.x, pipe) ? (int)grid.y : 1;
     if (ploop > 1) grid.y = 1;
@@ -100,142 +115,129 @@ void nt_kernel_launch_tr(hipStream_t s, dim3 grid, const AL& al, const BL& bl, c
 // layers), but makes the LDS halo-tile kernels 4-15 % slower (their stores were not the bound; the swapped fragments
 // cost LDS issue) -> halo kernels keep the per-element epilogue.
 
-template <typename T, int BM, int BN, int WM, int WN, bool TR, class AL, class BL, class EP>
+template <typename T, class TL>
+GemmPlan nt_plan(int M, int N, int Kmax, int phases) {
+    const int tmn = cdiv(M, TL::BM) * cdiv(N, TL::BN);
+    const Plan pl = plan_nt(tmn * phases, Kmax, gemm_bk<T>());
+    return {tmn, pl, (size_t)phases * pl.S * M * N * sizeof(float)};
+}
+// register path: short reductions keep the 4-chunk K-step (more co-resident blocks), long ones 8 chunks
+inline bool nt_long_k(int Kmax) { return Kmax >= 1024; }
+
+// The GEMM to the plan's fp32 partial slabs alone (S = 1: one slab); a reduce launch follows.
+template <typename T, class TL, bool TR, class AL, class BL>
+int nt_partials(hipStream_t s, const AL& al, const BL& bl, const GemmPlan& gp, int M, int N, int Kmax, int phases, Ws ws,
+                int pipe) {
+    HLMC_CHECK_ARG(ws.p && ws.bytes >= gp.slab_bytes, "split-K workspace too small");
+    StorePartialZ part;
+    part.ws = ws.p; part.M = M; part.N = N; part.S = gp.pl.S; part.phase = 0; part.split = 0;
+    nt_kernel_launch_tr<T, TL, TR>(s, dim3(gp.tiles, phases, gp.pl.S), al, bl, part, M, N, gp.pl.ksl, nt_long_k(Kmax),
+                                   pipe);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
+}
+
+template <typename T, class TL, bool TR, class AL, class BL, class EP>
 int launch_nt(hipStream_t s, const AL& al, const BL& bl, const EP& ep, int M, int N, int Kmax, int phases, Ws ws,
               ops::ColStats* st = nullptr, bool dma_ok = true) {
-    constexpr int BK = gemm_bk<T>();
-    const int tmn = cdiv(M, BM) * cdiv(N, BN);
-    Plan pl = plan_nt(tmn * phases, Kmax, BK);
-    dim3 grid(tmn, phases, pl.S);
-    // register path: short reductions keep the 4-chunk K-step (more co-resident blocks), long ones 8 chunks
-    const bool long_k = Kmax >= 1024;
-    const int pipe = (dma_ok && BN >= 32 && BM >= 64) ? nt_pipe_select(pl.ksl, pl.S, tmn * phases * pl.S) : 0;
+    const GemmPlan gp = nt_plan<T, TL>(M, N, Kmax, phases);
+    const int S = gp.pl.S, ksl = gp.pl.ksl;
+    const int pipe = (dma_ok && TL::BN >= 32 && TL::BM >= 64) ? nt_pipe_select(ksl, S, gp.tiles * phases * S) : 0;
     const bool stats = st && st->acc.on();
     if (st) st->done = false;
-    if (pl.S == 1 && stats) {  // single pass: the epilogue also emits the column statistics
-        WithStats<EP> eps;
-        static_cast<EP&>(eps) = ep;
-        eps.acc = st->acc;
-        nt_kernel_launch_tr<T, BM, BN, WM, WN, TR>(s, grid, al, bl, eps, M, N, pl.ksl, long_k, pipe);
+    if (S == 1) {  // single pass; with statistics the epilogue also emits the column statistics
+        const dim3 grid(gp.tiles, phases, 1);
+        const bool long_k = nt_long_k(Kmax);
+        if (stats) nt_kernel_launch_tr<T, TL, TR>(s, grid, al, bl, with_stats(ep, st->acc), M, N, ksl, long_k, pipe);
+        else nt_kernel_launch_tr<T, TL, TR>(s, grid, al, bl, ep, M, N, ksl, long_k, pipe);
         HLMC_LAUNCHED();
-        st->done = true;
+        if (stats) st->done = true;
         return HLMC_OK;
     }
-    if (pl.S == 1) {
-        nt_kernel_launch_tr<T, BM, BN, WM, WN, TR>(s, grid, al, bl, ep, M, N, pl.ksl, long_k, pipe);
-        HLMC_LAUNCHED();
-        return HLMC_OK;
-    }
-    size_t need = (size_t)phases * pl.S * M * N * sizeof(float);
-    HLMC_CHECK_ARG(ws.p && ws.bytes >= need, "split-K workspace too small");
-    StorePartialZ part;
-    part.ws = ws.p; part.M = M; part.N = N; part.S = pl.S; part.phase = 0; part.split = 0;
-    nt_kernel_launch_tr<T, BM, BN, WM, WN, TR>(s, grid, al, bl, part, M, N, pl.ksl, long_k, pipe);
-    HLMC_LAUNCHED();
-    if (stats && N % 64 == 0 && (double)phases * pl.S * M * N < 2147483648.0) {  // the reduce delivers them
+    const int rc = nt_partials<T, TL, TR>(s, al, bl, gp, M, N, Kmax, phases, ws, pipe);
+    if (rc != HLMC_OK) return rc;
+    const bool idx32 = (double)phases * S * M * N < 2147483648.0;  // 32-bit slab offsets
+    if (stats && N % 64 == 0 && idx32) {  // the reduce delivers them
         const int rows = phases * M, ntc = N / 64;
         // the tallest tile (fewest accumulator adds) that still gives >= 1024 blocks (A/B: 128 / 256 / 512 / 1024)
         const int RU = cdiv(rows, 128) * ntc >= 1024 ? 32 : cdiv(rows, 64) * ntc >= 1024 ? 16 : 8;
         const unsigned nb = (unsigned)(cdiv(rows, 4 * RU) * ntc);
         switch (RU) {
-            case 32: splitk_reduce_stats_kernel<EP, 32><<<nb, 256, 0, s>>>(ws.p, ep, M, N, pl.S, phases, st->acc); break;
-            case 16: splitk_reduce_stats_kernel<EP, 16><<<nb, 256, 0, s>>>(ws.p, ep, M, N, pl.S, phases, st->acc); break;
-            default: splitk_reduce_stats_kernel<EP, 8><<<nb, 256, 0, s>>>(ws.p, ep, M, N, pl.S, phases, st->acc); break;
+            case 32: splitk_reduce_stats_kernel<EP, 32><<<nb, 256, 0, s>>>(ws.p, ep, M, N, S, phases, st->acc); break;
+            case 16: splitk_reduce_stats_kernel<EP, 16><<<nb, 256, 0, s>>>(ws.p, ep, M, N, S, phases, st->acc); break;
+            default: splitk_reduce_stats_kernel<EP, 8><<<nb, 256, 0, s>>>(ws.p, ep, M, N, S, phases, st->acc); break;
         }
         HLMC_LAUNCHED();
         st->done = true;
         return HLMC_OK;
     }
-    int64_t total = (int64_t)phases * M * N;
-    if (N % 4 == 0 && (double)phases * pl.S * M * N < 2147483648.0 && ((uintptr_t)ws.p & 15) == 0) {
+    const int64_t total = (int64_t)phases * M * N;
+    const FastDiv dN((uint32_t)N), dM((uint32_t)M);
+    if (N % 4 == 0 && idx32 && ((uintptr_t)ws.p & 15) == 0) {
         const unsigned nb = (unsigned)((total / 4 + 255) / 256);
-        splitk_reduce4_kernel<EP><<<nb, 256, 0, s>>>(ws.p, ep, M, N, pl.S, phases, FastDiv((uint32_t)N), FastDiv((uint32_t)M));
-        HLMC_LAUNCHED();
-        return HLMC_OK;
+        splitk_reduce_kernel<4, EP><<<nb, 256, 0, s>>>(ws.p, ep, M, N, S, phases, dN, dM);
+    } else {
+        const int blocks = (int)std::min<int64_t>(4096, (total + 255) / 256);
+        splitk_reduce_kernel<1, EP><<<blocks, 256, 0, s>>>(ws.p, ep, M, N, S, phases, dN, dM);
     }
-    int blocks = (int)std::min<int64_t>(4096, (total + 255) / 256);
-    splitk_reduce_kernel<EP><<<blocks, 256, 0, s>>>(ws.p, ep, M, N, pl.S, phases);
     HLMC_LAUNCHED();
-    return HLMC_OK;
-}
-
-template <int BM, int BN>
-size_t nt_ws(int M, int N, int Kmax, int phases, int BK) {
-    const int tmn = cdiv(M, BM) * cdiv(N, BN);
-    Plan pl = plan_nt(tmn * phases, Kmax, BK);
-    return pl.S == 1 ? 0 : (size_t)phases * pl.S * M * N * sizeof(float);
-}
-
-// launch_nt's GEMM to the fp32 partial slabs alone, under the same plan (S = 1: one slab); the caller reduces them.
-// Register path, per-element epilogue (the dense layers' launches: arbitrary ld / K).
-template <typename T, int BM, int BN, int WM, int WN, class AL, class BL>
-int launch_nt_partials(hipStream_t s, const AL& al, const BL& bl, int M, int N, int K, Ws ws, int* S_out) {
-    constexpr int BK = gemm_bk<T>();
-    const int tmn = cdiv(M, BM) * cdiv(N, BN);
-    const Plan pl = plan_nt(tmn, K, BK);
-    HLMC_CHECK_ARG(ws.p && ws.bytes >= (size_t)pl.S * M * N * sizeof(float), "split-K workspace too small");
-    StorePartialZ part;
-    part.ws = ws.p; part.M = M; part.N = N; part.S = pl.S; part.phase = 0; part.split = 0;
-    nt_kernel_launch_tr<T, BM, BN, WM, WN, false>(s, dim3(tmn, 1, pl.S), al, bl, part, M, N, pl.ksl, K >= 1024, 0);
-    HLMC_LAUNCHED();
-    *S_out = pl.S;
     return HLMC_OK;
 }
 
 // Tile choice for the NT family by N: 128x128 / 128x64 / 128x32.  (Measured: stepping down to 64x64 to put
 // two blocks on every CU doubles operand re-reads and is slower on every layer of the step.)
-inline int nt_tile(int M, int N, int phases) {
+template <class F>
+auto with_nt_tile(int M, int N, int phases, F&& f) {
     // 128 x 64 tiles where 128 x 128 tiles would give an unsplit grid of target/2 .. target blocks (one block per
     // CU where two fit: the 2-stage ring and the register path hold two): twice the blocks, no split-K slabs.
     // Measured: 133.1k vs 132.3k clips/s (3 rounds); also for target/4 .. target/2 (then split-K) 131.3k.
-    if (N >= 128) {
-        const int t = cdiv(M, 128) * cdiv(N, 128) * phases;
-        if (t >= kNtTargetBlocks / 2 && t < kNtTargetBlocks) return 1;
-    }
-    if (N >= 128) return 0;
-    if (N > 32) return 1;
-    return 3;
+    const int t = cdiv(M, 128) * cdiv(N, 128) * phases;
+    if (N >= 128 && !(t >= kNtTargetBlocks / 2 && t < kNtTargetBlocks)) return f(Tile<128, 128, 64, 64>{});
+    if (N > 32) return f(Tile<128, 64, 32, 64>{});
+    return f(Tile<128, 32, 32, 32>{});
 }
 template <typename T, class AL, class BL, class EP>
 int dispatch_nt(hipStream_t s, const AL& al, const BL& bl, const EP& ep, int M, int N, int Kmax, int phases, Ws ws,
                 ops::ColStats* st = nullptr) {
-    // conv / sub-pixel outputs are NHWC rows of N (a multiple of 8) channels: transposed-accumulator epilogue
-    if (N % 4 == 0) {
-        switch (nt_tile(M, N, phases)) {
-            case 0: return launch_nt<T, 128, 128, 64, 64, true>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
-            case 1: return launch_nt<T, 128, 64, 32, 64, true>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
-            default: return launch_nt<T, 128, 32, 32, 32, true>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
-        }
-    }
-    switch (nt_tile(M, N, phases)) {
-        case 0: return launch_nt<T, 128, 128, 64, 64, false>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
-        case 1: return launch_nt<T, 128, 64, 32, 64, false>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
-        default: return launch_nt<T, 128, 32, 32, 32, false>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
-    }
+    return with_nt_tile(M, N, phases, [&](auto tl) {
+        using TL = decltype(tl);
+        // conv / sub-pixel outputs are NHWC rows of N (a multiple of 8) channels: transposed-accumulator epilogue
+        if (N % 4 == 0) return launch_nt<T, TL, true>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
+        return launch_nt<T, TL, false>(s, al, bl, ep, M, N, Kmax, phases, ws, st);
+    });
 }
+// workspace of a split launch: its slabs (none for S = 1)
+inline size_t split_ws(const GemmPlan& gp) { return gp.pl.S == 1 ? 0 : gp.slab_bytes; }
 template <typename T>
 size_t dispatch_nt_ws(int M, int N, int Kmax, int phases) {
-    constexpr int BK = gemm_bk<T>();
-    switch (nt_tile(M, N, phases)) {
-        case 0: return nt_ws<128, 128>(M, N, Kmax, phases, BK);
-        case 1: return nt_ws<128, 64>(M, N, Kmax, phases, BK);
-        case 2: return nt_ws<64, 64>(M, N, Kmax, phases, BK);
-        default: return nt_ws<128, 32>(M, N, Kmax, phases, BK);
-    }
+    return with_nt_tile(M, N, phases, [&](auto tl) { return split_ws(nt_plan<T, decltype(tl)>(M, N, Kmax, phases)); });
 }
 
-// Linear layers have small M (= batch): 64x64 tiles so more blocks exist before split-K.
+// Linear layers have small M (= batch): 64x64 tiles so more blocks exist before split-K.  Register path, per-element
+// epilogue: arbitrary ld / K (the DMA path needs 16-byte chunks that never straddle K).
+template <class F>
+auto with_linear_tile(int M, int N, F&& f) {
+    if (M >= 1024 && N >= 128) return f(Tile<128, 128, 64, 64>{});
+    return f(Tile<64, 64, 32, 32>{});
+}
 template <typename T, class AL, class BL, class EP>
 int dispatch_linear(hipStream_t s, const AL& al, const BL& bl, const EP& ep, int M, int N, int K, Ws ws) {
-    // register path: arbitrary ld / K (the DMA path needs 16-byte chunks that never straddle K)
-    if (M >= 1024 && N >= 128) return launch_nt<T, 128, 128, 64, 64, false>(s, al, bl, ep, M, N, K, 1, ws, nullptr, false);
-    return launch_nt<T, 64, 64, 32, 32, false>(s, al, bl, ep, M, N, K, 1, ws, nullptr, false);
+    return with_linear_tile(M, N, [&](auto tl) {
+        return launch_nt<T, decltype(tl), false>(s, al, bl, ep, M, N, K, 1, ws, nullptr, false);
+    });
 }
 template <typename T>
 size_t dispatch_linear_ws(int M, int N, int K) {
-    constexpr int BK = gemm_bk<T>();
-    if (M >= 1024 && N >= 128) return nt_ws<128, 128>(M, N, K, 1, BK);
-    return nt_ws<64, 64>(M, N, K, 1, BK);
+    return with_linear_tile(M, N, [&](auto tl) { return split_ws(nt_plan<T, decltype(tl)>(M, N, K, 1)); });
+}
+// dispatch_linear's GEMM to the partial slabs alone; the caller reduces the *S_out slabs.
+template <typename T, class AL, class BL>
+int dispatch_linear_partials(hipStream_t s, const AL& al, const BL& bl, int M, int N, int K, Ws ws, int* S_out) {
+    return with_linear_tile(M, N, [&](auto tl) {
+        const GemmPlan gp = nt_plan<T, decltype(tl)>(M, N, K, 1);
+        *S_out = gp.pl.S;
+        return nt_partials<T, decltype(tl), false>(s, al, bl, gp, M, N, K, 1, ws, 0);
+    });
 }
 
 // Final epilogue of a conv weight gradient: C[m][n = tap*C + ci] -> dW[m][ci][tap] (torch layout).
@@ -262,64 +264,29 @@ struct StoreWgradConv {
 };
 
 // Split-K reduction of a conv weight gradient into torch's [M][C][3][3] layout for few splits (S <= 4: the deep
-// layers, whose 2-9 MB outputs dominate): one 288-thread block per (row m, 32 input channels) sums the 9 taps x 32
-// channels in split order (the slab reads: 9 runs of 32 consecutive floats) and writes the block's 288 consecutive
-// dW floats through LDS.  (splitk_reduce_grouped_kernel stores dW[m][ci][tap] from the GEMM's (tap, ci) column
-// order: stride-9 scattered 4-byte stores, 10-13 us for these layers.)
+// layers, whose 2-9 MB outputs dominate): one 288-thread block per (row m, 32 VW input channels); thread (tap, cl) sums
+// VW consecutive channels of its tap in split order (slab_sum: the same bits at either width; the slab reads: 9 runs
+// of 32 VW consecutive floats) and the block writes its 288 VW consecutive dW floats through LDS.
+// (splitk_reduce_grouped_kernel stores dW[m][ci][tap] from the GEMM's (tap, ci) column order: stride-9 scattered
+// 4-byte stores, 10-13 us for these layers.)  VW 4 (C % 128 == 0, 16-byte aligned ws and dW): 16-byte slab loads and
+// dW stores.  (Four-byte loads left too few bytes in flight: 2.6-3.5 TB/s on the 2- and 4-split layers.)
+template <int VW>
 __global__ __launch_bounds__(288) void splitk_reduce_wgrad_conv_kernel(const float* __restrict__ ws, StoreWgradConv ep,
                                                                        int M, int C, int S) {
     ep_extra(ep, 0);
-    __shared__ float tile[288];
-    const int cb = C / 32;
-    const int m = blockIdx.x / cb, ci0 = (blockIdx.x - m * cb) * 32;
+    constexpr int CB = 32 * VW;  // input channels per block
+    __shared__ __attribute__((aligned(16))) float tile[CB * 9];
+    const int cb = C / CB;
+    const int m = blockIdx.x / cb, ci0 = (blockIdx.x - m * cb) * CB;
     const int t = threadIdx.x, tap = t >> 5, cl = t & 31;
     const int64_t N = 9LL * C, st = (int64_t)M * N;
-    const float* p = ws + (int64_t)m * N + tap * C + ci0 + cl;
-    float acc = 0.f;
-    int k = 0;
-    for (; k + 3 < S; k += 4) {
-        const float a0 = p[k * st], a1 = p[(k + 1) * st], a2 = p[(k + 2) * st], a3 = p[(k + 3) * st];
-        acc += a0; acc += a1; acc += a2; acc += a3;
-    }
-    for (; k < S; ++k) acc += p[k * st];
-    tile[cl * 9 + tap] = acc;
+    const slab_t<VW> acc = slab_sum<VW, 1>(ws + (int64_t)m * N + tap * C + ci0 + VW * cl, st, S, 0);
+#pragma unroll
+    for (int i = 0; i < VW; ++i) tile[(VW * cl + i) * 9 + tap] = slab_at(acc, i);
     __syncthreads();
-    ep.dW[(int64_t)m * N + (int64_t)ci0 * 9 + t] = tile[t];
-}
-
-// The same for C % 128 == 0 with 16-byte slab loads: a 288-thread block per (row m, 128 input channels), each thread
-// summing 4 consecutive channels of one tap in split order (the same order, so the same bits, as the kernel above),
-// the block's 1,152 consecutive dW floats written as float4 through LDS.  (Four-byte loads left too few bytes in
-// flight: 2.6-3.5 TB/s on the 2- and 4-split layers.)
-__global__ __launch_bounds__(288) void splitk_reduce_wgrad_conv4_kernel(const float* __restrict__ ws, StoreWgradConv ep,
-                                                                        int M, int C, int S) {
-    ep_extra(ep, 0);
-    __shared__ __attribute__((aligned(16))) float tile[128 * 9];
-    const int cb = C / 128;
-    const int m = blockIdx.x / cb, ci0 = (blockIdx.x - m * cb) * 128;
-    const int t = threadIdx.x, tap = t >> 5, cl = t & 31;
-    const int64_t N = 9LL * C, st = (int64_t)M * N;
-    const float* p = ws + (int64_t)m * N + tap * C + ci0 + 4 * cl;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    int k = 0;
-    for (; k + 3 < S; k += 4) {
-        const float4 a0 = *reinterpret_cast<const float4*>(p + k * st), a1 = *reinterpret_cast<const float4*>(p + (k + 1) * st);
-        const float4 a2 = *reinterpret_cast<const float4*>(p + (k + 2) * st), a3 = *reinterpret_cast<const float4*>(p + (k + 3) * st);
-        acc.x += a0.x; acc.y += a0.y; acc.z += a0.z; acc.w += a0.w;
-        acc.x += a1.x; acc.y += a1.y; acc.z += a1.z; acc.w += a1.w;
-        acc.x += a2.x; acc.y += a2.y; acc.z += a2.z; acc.w += a2.w;
-        acc.x += a3.x; acc.y += a3.y; acc.z += a3.z; acc.w += a3.w;
-    }
-    for (; k < S; ++k) {
-        const float4 a = *reinterpret_cast<const float4*>(p + k * st);
-        acc.x += a.x; acc.y += a.y; acc.z += a.z; acc.w += a.w;
-    }
-    tile[(4 * cl + 0) * 9 + tap] = acc.x;
-    tile[(4 * cl + 1) * 9 + tap] = acc.y;
-    tile[(4 * cl + 2) * 9 + tap] = acc.z;
-    tile[(4 * cl + 3) * 9 + tap] = acc.w;
-    __syncthreads();
-    *reinterpret_cast<float4*>(ep.dW + (int64_t)m * N + (int64_t)ci0 * 9 + 4 * t) = *reinterpret_cast<const float4*>(&tile[4 * t]);
+    using V = slab_t<VW>;
+    *reinterpret_cast<V*>(ep.dW + (int64_t)m * N + (int64_t)ci0 * 9 + VW * t) =
+        *reinterpret_cast<const V*>(&tile[VW * t]);
 }
 
 // S-way split-K reduction with the splits spread over G thread groups (splitk_reduce_grouped_kernel)
@@ -327,11 +294,11 @@ template <class EP>
 void reduce_splits(hipStream_t s, const float* ws, const EP& ep, int M, int N, int S) {
     if constexpr (std::is_same<EP, StoreWgradConv>::value) {
         if (S <= 4 && ep.C % 128 == 0 && (((uintptr_t)ws | (uintptr_t)ep.dW) & 15) == 0) {
-            splitk_reduce_wgrad_conv4_kernel<<<(unsigned)(M * (ep.C / 128)), 288, 0, s>>>(ws, ep, M, ep.C, S);
+            splitk_reduce_wgrad_conv_kernel<4><<<(unsigned)(M * (ep.C / 128)), 288, 0, s>>>(ws, ep, M, ep.C, S);
             return;
         }
         if (S <= 4 && ep.C % 32 == 0) {
-            splitk_reduce_wgrad_conv_kernel<<<(unsigned)(M * (ep.C / 32)), 288, 0, s>>>(ws, ep, M, ep.C, S);
+            splitk_reduce_wgrad_conv_kernel<1><<<(unsigned)(M * (ep.C / 32)), 288, 0, s>>>(ws, ep, M, ep.C, S);
             return;
         }
     }
@@ -341,8 +308,8 @@ void reduce_splits(hipStream_t s, const float* ws, const EP& ep, int M, int N, i
         constexpr int G = decltype(gtag)::value;
         const int64_t per = v4 ? 4 * (256 / G) : 256 / G;  // outputs per block
         const int64_t blocks = (total + per - 1) / per;
-        if (v4) splitk_reduce_grouped4_kernel<G, EP><<<(unsigned)blocks, 256, 0, s>>>(ws, ep, M, N, S);
-        else splitk_reduce_grouped_kernel<G, EP><<<(unsigned)blocks, 256, 0, s>>>(ws, ep, M, N, S);
+        if (v4) splitk_reduce_grouped_kernel<4, G, EP><<<(unsigned)blocks, 256, 0, s>>>(ws, ep, M, N, S);
+        else splitk_reduce_grouped_kernel<1, G, EP><<<(unsigned)blocks, 256, 0, s>>>(ws, ep, M, N, S);
     };
     if (S >= 32) go(std::integral_constant<int, 8>{});
     else if (S >= 8) go(std::integral_constant<int, 4>{});
@@ -350,14 +317,19 @@ void reduce_splits(hipStream_t s, const float* ws, const EP& ep, int M, int N, i
     else go(std::integral_constant<int, 1>{});
 }
 
-template <typename T, int BM, int BN, int WM, int WN, class LL, class HL, class EP>
+template <typename T, class TL>
+GemmPlan tn_plan(int M, int N, int K) {
+    const int tiles = cdiv(M, TL::BM) * cdiv(N, TL::BN);
+    const Plan pl = plan_tn(tiles, K, gemm_bk<T>());
+    return {tiles, pl, (size_t)pl.S * M * N * sizeof(float)};
+}
+template <typename T, class TL, class LL, class HL, class EP>
 int launch_tn(hipStream_t s, const LL& ll, const HL& hl, const EP& ep, int M, int N, int K, Ws ws) {
-    constexpr int BK = gemm_bk<T>();
-    const int tiles = cdiv(M, BM) * cdiv(N, BN);
-    Plan pl = plan_tn(tiles, K, BK);
-    size_t need = (size_t)pl.S * M * N * sizeof(float);
-    HLMC_CHECK_ARG(ws.p && ws.bytes >= need, "wgrad workspace too small");
-    dim3 grid(tiles, 1, pl.S);
+    constexpr int BM = TL::BM, BN = TL::BN, WM = TL::WM, WN = TL::WN;
+    const GemmPlan gp = tn_plan<T, TL>(M, N, K);
+    const Plan pl = gp.pl;
+    HLMC_CHECK_ARG(ws.p && ws.bytes >= gp.slab_bytes, "wgrad workspace too small");
+    dim3 grid(gp.tiles, 1, pl.S);
     const int rm = xcd_remap_for_site();
     HLMC_PROBE_BEGIN(s);
     // the 64-deep K-step for splits of >= 1024 rows (measured: 490.9 vs 450.9 us for the 9 conv layers when
@@ -389,11 +361,6 @@ int launch_tn(hipStream_t s, const LL& ll, const HL& hl, const EP& ep, int M, in
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
-template <int BM, int BN>
-size_t tn_ws(int M, int N, int K, int BK) {
-    Plan pl = plan_tn(cdiv(M, BM) * cdiv(N, BN), K, BK);
-    return (size_t)pl.S * M * N * sizeof(float);
-}
 
 // Weight-gradient tile choice.  Weight gradients reduce over K = B * pixels (16 k - 262 k) into a small
 // M x N output; the grid is filled by split-K.  Conv weight gradients have N = 9 C: C = 32 gives N = 288,
@@ -401,32 +368,19 @@ size_t tn_ws(int M, int N, int K, int BK) {
 // the 64 x 288 x 262144 layers).  (Measured and rejected: 64 x 64 tiles everywhere, which cut the split-K slab
 // bytes 3-4x but were 10-35 % slower per layer — the kernel is bound by per-block load latency, not slabs.)
 inline bool tn_n96(int N) { return N % 128 != 0 && N % 96 == 0; }
-// 0: 128x128, 1: 64x128, 2: 64x96, 3: 32x128
-inline int tn_tile(int M, int N) {
-    if (M >= 128) return 0;
-    if (M > 32) return tn_n96(N) ? 2 : 1;
-    return 3;
+template <class F>
+auto with_tn_tile(int M, int N, F&& f) {
+    if (M >= 128) return f(Tile<128, 128, 64, 64>{});
+    if (M > 32) return tn_n96(N) ? f(Tile<64, 96, 32, 48>{}) : f(Tile<64, 128, 32, 64>{});
+    return f(Tile<32, 128, 32, 32>{});
 }
 template <typename T, class LL, class HL, class EP>
 int dispatch_tn(hipStream_t s, const LL& ll, const HL& hl, const EP& ep, int M, int N, int K, Ws ws) {
-    switch (tn_tile(M, N)) {
-        case 0: return launch_tn<T, 128, 128, 64, 64>(s, ll, hl, ep, M, N, K, ws);
-        case 1: return launch_tn<T, 64, 128, 32, 64>(s, ll, hl, ep, M, N, K, ws);
-        case 2: return launch_tn<T, 64, 96, 32, 48>(s, ll, hl, ep, M, N, K, ws);
-        default: return launch_tn<T, 32, 128, 32, 32>(s, ll, hl, ep, M, N, K, ws);
-    }
+    return with_tn_tile(M, N, [&](auto tl) { return launch_tn<T, decltype(tl)>(s, ll, hl, ep, M, N, K, ws); });
 }
 template <typename T>
-size_t dispatch_tn_ws(int M, int N, int K) {
-    constexpr int BK = gemm_bk<T>();
-    size_t w = 0;
-    switch (tn_tile(M, N)) {
-        case 0: w = tn_ws<128, 128>(M, N, K, BK); break;
-        case 1: w = tn_ws<64, 128>(M, N, K, BK); break;
-        case 2: w = tn_ws<64, 96>(M, N, K, BK); break;
-        default: w = tn_ws<32, 128>(M, N, K, BK); break;
-    }
-    return w;
+size_t dispatch_tn_ws(int M, int N, int K) {  // slabs at every split count (only a direct epilogue skips S = 1's)
+    return with_tn_tile(M, N, [&](auto tl) { return tn_plan<T, decltype(tl)>(M, N, K).slab_bytes; });
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -492,10 +446,8 @@ int halo_launch(hipStream_t s, const HaloShape<EP>& h, const bf16* x, int Hi, co
     const int grid = std::min(ntiles * g.nspl, g.cap);
     HLMC_PROBE_BEGIN(s);
     if (stats) {
-        WithStats<EP> eps;
-        static_cast<EP&>(eps) = ep;
-        eps.acc = st->acc;
-        (xin ? h.k_xin : h.k_stats)<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, eps, M, xin ? *xin : ops::BnInput{});
+        (xin ? h.k_xin : h.k_stats)<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, with_stats(ep, st->acc), M,
+                                                         xin ? *xin : ops::BnInput{});
     } else {
         h.k_plain<<<grid, 256, 0, s>>>(x, Hi, ntiles, wp, ep, M, ops::BnInput{});
     }
@@ -600,8 +552,8 @@ int wgrad_s2(hipStream_t s, const T* L, int B, int Hl, int Wl, int M, const T* X
         KRowConvS2P2<T> hl{Xh, lh, lw, lc, K, (uint32_t)xbytes};
         return dispatch_tn<T>(s, ll, hl, ep, M, N, K, ws);
     }
-    KRowDense<T> ll{L, M, K, M, aligned16(L)};
-    KRowConvS2<T> hl{Xh, Hl, Wl, C, K, FastDiv((uint32_t)Wl), FastDiv((uint32_t)Hl)};
+    KRowDense<T> ll{{}, L, M, K, M, aligned16(L)};
+    KRowConvS2<T> hl{{}, Xh, Hl, Wl, C, K, FastDiv((uint32_t)Wl), FastDiv((uint32_t)Hl)};
     return dispatch_tn<T>(s, ll, hl, ep, M, N, K, ws);
 }
 template <typename T>
@@ -648,9 +600,7 @@ int linear_partials(hipStream_t s, const T* x, int ldx, int M, int K, const T* w
     DenseLoader<T> al{x, ldx, M, K, (ldx % V == 0) && aligned16(x)};
     DenseLoader<T> bl{w, ldw, N, K, (ldw % V == 0) && aligned16(w)};
     probe::site(probe::kLinear, 2.0 * M * N * K, (double)sizeof(T) * ((double)M * K + (double)N * K) + 4.0 * M * N);
-    // dispatch_linear's tiles and plan
-    if (M >= 1024 && N >= 128) return launch_nt_partials<T, 128, 128, 64, 64>(s, al, bl, M, N, K, ws, S_out);
-    return launch_nt_partials<T, 64, 64, 32, 32>(s, al, bl, M, N, K, ws, S_out);
+    return dispatch_linear_partials<T>(s, al, bl, M, N, K, ws, S_out);
 }
 template <typename T>
 size_t linear_partials_ws(int M, int K, int N) {
@@ -680,8 +630,8 @@ template <typename T>
 int linear_wgrad(hipStream_t s, const T* dy, int lddy, const T* x, int ldx, int Mb, int N, int K, float* dW, float* db,
                  Ws ws) {
     constexpr int V = Vec16<T>::N;
-    KRowDense<T> ll{dy, lddy, Mb, N, (lddy % V == 0) && aligned16(dy), false};
-    KRowDense<T> hl{x, ldx, Mb, K, (ldx % V == 0) && aligned16(x), db != nullptr};
+    KRowDense<T> ll{{}, dy, lddy, Mb, N, (lddy % V == 0) && aligned16(dy), false};
+    KRowDense<T> hl{{}, x, ldx, Mb, K, (ldx % V == 0) && aligned16(x), db != nullptr};
     probe::site(probe::kLinearWgrad, 2.0 * N * K * Mb, (double)sizeof(T) * ((double)Mb * N + (double)Mb * K) + 4.0 * N * K);
     if (db) return dispatch_tn<T>(s, ll, hl, StoreWgradBias{dW, db, K}, N, K + 1, Mb, ws);
     StoreRM<float> ep{dW, nullptr, K, 0, 0};
@@ -713,8 +663,8 @@ int linear_wgrad_pair(hipStream_t s, const T* dy, int lddy, const T* x, int ldx,
     constexpr int V = Vec16<T>::N;
     HLMC_CHECK_ARG(dW1 && db1 && dW2 && db2, "linear_wgrad_pair: gradients required");
     const int N = 2 * N1;
-    KRowDense<T> ll{dy, lddy, Mb, N, (lddy % V == 0) && aligned16(dy), false};
-    KRowDense<T> hl{x, ldx, Mb, K, (ldx % V == 0) && aligned16(x), true};
+    KRowDense<T> ll{{}, dy, lddy, Mb, N, (lddy % V == 0) && aligned16(dy), false};
+    KRowDense<T> hl{{}, x, ldx, Mb, K, (ldx % V == 0) && aligned16(x), true};
     probe::site(probe::kLinearWgrad, 2.0 * N * K * Mb, (double)sizeof(T) * ((double)Mb * N + (double)Mb * K) + 4.0 * N * K);
     return dispatch_tn<T>(s, ll, hl, StoreWgradBiasPair{dW1, db1, dW2, db2, K, N1}, N, K + 1, Mb, ws);
 }

@@ -83,7 +83,12 @@ def test_subpixel_convT(cuda, ws, dt, B, Hi, Wi, Ci, Co):
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 @pytest.mark.parametrize("B,Hl,Wl,M,C", [(2, 8, 8, 64, 32), (2, 4, 4, 128, 64), (2, 2, 2, 512, 256),
                                         (3, 1, 1, 512, 512), (2, 16, 16, 32, 64), (4, 2, 8, 256, 128),
-                                        (3, 8, 32, 64, 32), (1, 32, 32, 64, 32)])
+                                        (3, 8, 32, 64, 32), (1, 32, 32, 64, 32),
+                                        # the conv-layout split-K reduces (plan_tn; G: the grouped reduce's groups)
+                                        (8, 8, 8, 128, 128),    # bf16 S 2 / fp32 S 4: 16-byte conv reduce (C % 128)
+                                        (16, 8, 8, 128, 128),   # bf16 S 4: 16-byte conv reduce; fp32 S 8: grouped, G 4
+                                        (12, 8, 8, 64, 32),     # 96-wide; bf16 S 3: 4-byte conv reduce, tail; fp32 S 6: G 2
+                                        (2, 4, 4, 16, 16)])     # S 1, C % 32 != 0: the grouped reduce's scattered store
 def test_wgrad_s2_conv(cuda, ws, dt, B, Hl, Wl, M, C):
     """Conv2d weight gradient: L = dY (low-res, M=Co), Xh = X (high-res, C=Ci), through the weight-gradient TN GEMM
     (the B = 256 bench shapes are test_wgrad_s2_bench_shapes_bf16)."""
@@ -122,7 +127,11 @@ def test_wgrad_s2_convT(cuda, ws, dt):
 @pytest.mark.parametrize("M,K,N,ldx,act,acc", [(4, 768, 256, 768, 0, 0), (256, 2048, 1024, 2048, 0, 0),
                                               (5, 370, 128, 376, 1, 0), (256, 2314, 64, 2320, 0, 1),
                                               (33, 128, 1152, 136, 1, 0), (256, 74, 2304, 80, 0, 0),
-                                              (2, 1024, 16384, 1152, 0, 0), (2, 1024, 16384, 1152, 0, 1)])
+                                              (2, 1024, 16384, 1152, 0, 0), (2, 1024, 16384, 1152, 0, 1),
+                                              # N % 4 != 0: the scalar NT split-K reduce (plan_nt, one 64 x 64 tile)
+                                              (3, 384, 42, 384, 0, 0),   # bf16 S 3: tail only; fp32 S 6: 4 + 2
+                                              (3, 512, 42, 512, 0, 0),   # bf16 S 4: one group of 4, no tail; fp32 S 8
+                                              (3, 896, 42, 896, 0, 1)])  # bf16 S 7: 4 + 3; fp32 S 14: 4 + 4 + 4 + 2
 def test_linear(cuda, ws, dt, M, K, N, ldx, act, acc):
     code, tdt, tol = DT[dt]
     g = torch.Generator().manual_seed(M + K + N)
@@ -170,7 +179,13 @@ def test_linear_relu_mask(cuda, ws, dt, M, K, N, acc):
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 @pytest.mark.parametrize("Mb,N,K", [(4, 256, 768), (256, 1024, 2048), (32, 128, 370), (256, 64, 2314),
-                                    (7, 2048, 1024)])
+                                    (7, 2048, 1024),
+                                    # the grouped TN reduce at both widths (8 columns: float4; 9 with the bias: scalar),
+                                    # one 32 x 128 tile (plan_tn): S (G groups) fp32 / bf16
+                                    (300, 8, 8),     # 2, ragged (1) / 1 (1)
+                                    (512, 8, 8),     # 4 (2) / 2 (1)
+                                    (1024, 8, 8),    # 8 (4) / 4 (2)
+                                    (4096, 8, 8)])   # 32 (8) / 16 (4)
 def test_linear_wgrad(cuda, ws, dt, Mb, N, K):
     code, tdt, tol = DT[dt]
     g = torch.Generator().manual_seed(Mb + N + K)
