@@ -9,6 +9,8 @@ Drop-in surface (reference names):
   KMeans                                       (sklearn KMeans calls of the three model scripts)
   DBSCAN, dbscan_eps_sweep                     (sklearn DBSCAN and the eps search of src/Convolutional_VAE.py)
   AgglomerativeClustering, agglomerative_k_sweep   (sklearn's Ward clustering and its k sweep, same script)
+  PCA, pca_kmeans_baseline                     (sklearn PCA and the "PCA + KMeans" rows of src/Simple_VAE.py and
+                                                src/Conditional_VAE.py)
   metrics.silhouette_score / davies_bouldin_score / calinski_harabasz_score / adjusted_rand_score /
   normalized_mutual_info_score / calculate_purity   (the sklearn.metrics evaluation calls)
   Adam                                         (torch.optim.Adam of the train loops)
@@ -22,6 +24,8 @@ from .cluster import DBSCAN, AgglomerativeClustering, KMeans, agglomerative_k_sw
 from .features import (SPECTRAL_FEATURES, StandardScaler, chroma_stft, extract_mel_spectrogram, extract_spectral_features,
                        mean_std_pool, mel_filterbank, melspectrogram, mfcc, power_to_db, rms, spectral_bandwidth,
                        spectral_centroid, spectral_rolloff, spectral_stats, zero_crossing_rate)
+from .decomposition import PCA, pca_kmeans_baseline
+from . import decomposition
 from . import metrics
 from . import preprocess
 from .losses import cvae_loss_function, loss_function, vae_loss
@@ -33,4 +37,5 @@ from . import pipeline
 __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_function", "vae_loss", "melspectrogram",
            "power_to_db", "mfcc", "extract_mel_spectrogram", "mean_std_pool", "mel_filterbank", "StandardScaler",
            "KMeans", "DBSCAN", "dbscan_eps_sweep", "AgglomerativeClustering", "agglomerative_k_sweep",
+           "PCA", "pca_kmeans_baseline",
            "Adam", "Trainer", "GraphedStep", "metrics"]

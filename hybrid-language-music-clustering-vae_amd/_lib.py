@@ -111,6 +111,9 @@ _SIGS = {
     "hlmc_ward_workspace": (c_i64, [c_i64]),
     "hlmc_ward_pdist": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
     "hlmc_ward_chain": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_pca_workspace": (c_i64, [c_i64, c_int]),
+    "hlmc_pca_cov": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_pca_project": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
     "hlmc_op_conv_s2": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_op_subpixel": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_op_wgrad_s2": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_i64]),

@@ -467,6 +467,16 @@ int hlmc_ward_chain(void* stream, int64_t n, double* D, int32_t* merge_a, int32_
     return ward::chain(S(stream), n, D, merge_a, merge_b, merge_dist, merge_size, ws, ws_bytes < 0 ? 0 : (size_t)ws_bytes);
 }
 
+// ------------------------------------------------------------------------------------ PCA
+int64_t hlmc_pca_workspace(int64_t n, int d) { return (int64_t)pca::workspace(n, d); }
+int hlmc_pca_cov(void* stream, const float* X, int64_t n, int d, double* mean, double* G, void* ws, int64_t ws_bytes) {
+    return pca::cov(S(stream), X, n, d, mean, G, ws, ws_bytes < 0 ? 0 : (size_t)ws_bytes);
+}
+int hlmc_pca_project(void* stream, const float* A, int64_t n, int p, const double* B, int q, const double* a_off,
+                     const double* o_off, float* out) {
+    return pca::project(S(stream), A, n, p, B, q, a_off, o_off, out);
+}
+
 // ------------------------------------------------------------------------------------ op-level entries
 // Individual GEMM-family kernels (the building blocks of hlmc_net_*), exposed for testing and reuse.
 #define DT_DISPATCH(dtype, CALL_F32, CALL_BF16) ((dtype) == HLMC_BF16 ? (CALL_BF16) : (CALL_F32))

@@ -110,4 +110,13 @@ int chain(hipStream_t s, int64_t n, double* D, int32_t* merge_a, int32_t* merge_
           int32_t* merge_size, void* ws, size_t ws_bytes);
 }  // namespace ward
 
+// PCA (pca.hip): the float64 column mean and centred Gram matrix of float32 rows, and the float64-accumulated
+// projection out = (A - a_off) B + o_off, both on the fp64 MFMA; the d x d eigen-solve stays on the host.
+namespace pca {
+size_t workspace(int64_t n, int d);
+int cov(hipStream_t s, const float* X, int64_t n, int d, double* mean, double* G, void* ws, size_t ws_bytes);
+int project(hipStream_t s, const float* A, int64_t n, int p, const double* B, int q, const double* a_off,
+            const double* o_off, float* out);
+}  // namespace pca
+
 }  // namespace hlmc

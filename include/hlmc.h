@@ -378,6 +378,34 @@ int hlmc_ward_pdist(void* stream, const float* X, int64_t n, int d, double* D);
 int hlmc_ward_chain(void* stream, int64_t n, double* D /* in, destroyed */, int32_t* merge_a, int32_t* merge_b,
                     double* merge_dist, int32_t* merge_size, void* ws, int64_t ws_bytes);
 
+/* ---- PCA ------------------------------------------------------------------------------------------------------------
+ * sklearn.decomposition.PCA(n_components=k).fit_transform at src/Simple_VAE.py:258-263 (370 -> 32) and
+ * src/Conditional_VAE.py:422-425 (290 -> 64): the two float64 GEMMs of the exact decomposition on the fp64 MFMA; the
+ * d x d eigen-solve between them is the caller's (hlmc_amd.PCA runs numpy.linalg.eigh on the host).
+ *
+ * hlmc_pca_cov: mean [d] float64 and G [d][d] float64, row-major, full and symmetric bit for bit:
+ *   mean_c = (sum_r x_rc) / n,   G[i][j] = sum_r ((double)x_ri - mean_i) ((double)x_rj - mean_j).
+ * X [n][d] f32, 2 <= n <= 2^24, 1 <= d <= 1024.  The rows are cut into S = ceil(n / L) slabs of
+ * L = max(256, ceil(n / 128) rounded up to a multiple of 32) rows (S <= 128, a function of n alone); every sum runs in
+ * a fixed order and the slabs are added in slab order, so the result is bit-identical from run to run.
+ * |G' - G|_ij <= (n + 8) 2^-53 sum_r |xc_ri| |xc_rj| + n |dm_i| |dm_j| with |dm_c| <= n 2^-53 mean_r |x_rc| the error
+ * of the mean (assuming the MFMA rounds each product and each addition of its 4-step inner sum at most once).
+ * Workspace (hlmc_pca_workspace bytes), T = ceil(d / 64) feature tiles, P = T (T + 1) / 2 tile pairs numbered row-major
+ * over the upper triangle ((0,0) (0,1) .. (0,T-1) (1,1) ..):
+ *   [colsum: float64 [S][d], the slabs' column sums, rounded up to 256 bytes]
+ *   [part:   float64 [S][P][64][64], slab s's share of the tile (ti, tj): part[s][pair][i][j] belongs to
+ *            G[64 ti + i][64 tj + j]; entries past d are 0, and of a diagonal pair only i <= j is used]
+ * G[a][b] for a <= b is part[0] + part[1] + ... + part[S-1] of its entry, added in that order.
+ *
+ * hlmc_pca_project: out [n][q] f32, out[r][j] = (float)(sum_c ((double)A[r][c] - a_off[c]) B[c][j] + o_off[j]),
+ * accumulated in float64 and rounded once.  A [n][p] f32, B [p][q] float64, a_off [p] and o_off [q] float64 or NULL
+ * (= 0).  n >= 1 (below 2^31), 1 <= p, q <= 1024.  transform: a_off = mean, B = components^T; inverse_transform:
+ * B = components, o_off = mean; whitening: a scaled B. */
+int64_t hlmc_pca_workspace(int64_t n, int d);      /* bytes; 0 when n or d is out of range */
+int hlmc_pca_cov(void* stream, const float* X, int64_t n, int d, double* mean, double* G, void* ws, int64_t ws_bytes);
+int hlmc_pca_project(void* stream, const float* A, int64_t n, int p, const double* B, int q, const double* a_off,
+                     const double* o_off, float* out);
+
 
 /* ============================================================== op-level entry points
  * The kernels hlmc_net_* is built from, on NHWC activations (dtype HLMC_F32 / HLMC_BF16 for x, y, packed
