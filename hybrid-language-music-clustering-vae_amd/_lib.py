@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -188,6 +189,22 @@ def require_cuda(*tensors):
             raise HLMCError("libhlmc operates on GPU tensors; got a CPU tensor")
         if t is not None and not t.is_contiguous():
             raise HLMCError("libhlmc needs contiguous tensors")
+
+
+def device_matrix(X, device=None, *, finite=False):
+    """X (a tensor, or anything numpy accepts) as a contiguous float32 [n_samples, n_features] tensor on the device:
+    the explicit ``device``, else a CUDA tensor's own, else the current CUDA device.  The shape, and with ``finite``
+    the absence of NaN / infinity (sklearn's check_array), are checked where X lives, before any copy to another
+    device, and on the float32 values the kernels will read: a finite float64 above float32's range is infinity."""
+    X = X.detach() if torch.is_tensor(X) else torch.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float32)))
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("X must be 2-D [n_samples, n_features] with at least one row and one column")
+    X = X.to(torch.float32)
+    if finite and not bool(torch.isfinite(X).all()):
+        raise ValueError("Input X contains NaN or infinity.")
+    if device is None:
+        device = X.device if X.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return X.to(device=torch.device(device)).contiguous()
 
 
 def vp_array(values):

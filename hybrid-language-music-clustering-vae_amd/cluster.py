@@ -314,24 +314,17 @@ class KMeans:
                 best = r
         return best
 
-    @staticmethod
-    def _require_finite(Xd):
-        """sklearn's check_array rejects NaN / infinity.  Here it is also what keeps the kernels in bounds: a
+    def _device_x(self, X):
+        """Rejecting NaN / infinity is sklearn's check_array.  Here it is also what keeps the kernels in bounds: a
         non-finite centre compares below no distance, the E-step then stores no cluster index and the kernels
         after it index the centres with the labels unchecked."""
-        if Xd.dim() != 2 or Xd.shape[0] < 1 or Xd.shape[1] < 1:
-            raise ValueError("X must be 2-D [n_samples, n_features] with at least one row and one column")
-        if not bool(torch.isfinite(Xd).all()):
-            raise ValueError("Input X contains NaN or infinity.")
+        return L.device_matrix(X, self._dev(), finite=True)
 
     # ------------------------------------------------------------------ sklearn API
     def fit(self, X, y=None, sample_weight=None):
         if sample_weight is not None:
             raise ValueError("sample_weight is not supported (the reference never passes it)")
-        dev = self._dev()
-        Xd = torch.as_tensor(np.asarray(X, dtype=np.float32) if not torch.is_tensor(X) else X, device=dev)
-        Xd = Xd.to(torch.float32).contiguous()
-        self._require_finite(Xd)
+        Xd = self._device_x(X)
         n, d = Xd.shape
         if n < self.n_clusters:
             raise ValueError(f"n_samples={n} should be >= n_clusters={self.n_clusters}")
@@ -371,10 +364,8 @@ class KMeans:
         return self.fit(X, sample_weight=sample_weight).labels_
 
     def predict(self, X):
-        dev = self._dev()
-        Xd = torch.as_tensor(np.asarray(X, dtype=np.float32) if not torch.is_tensor(X) else X, device=dev)
-        Xd = Xd.to(torch.float32).contiguous()
-        self._require_finite(Xd)
+        Xd = self._device_x(X)
+        dev = Xd.device
         n, d = Xd.shape
         if d != self.cluster_centers_.shape[1]:
             raise ValueError(f"X has {d} features, but KMeans was fitted with {self.cluster_centers_.shape[1]}")
@@ -395,18 +386,6 @@ def _radius_sq(eps):
     distances are compared with is float64(float32(float32(eps) * float32(eps))), not eps ** 2."""
     e = np.float32(eps)
     return float(np.float32(e * e))
-
-
-def _dbscan_device_x(X, device):
-    if torch.is_tensor(X):
-        dev = torch.device(device) if device is not None else (X.device if X.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-        Xd = X.detach().to(device=dev, dtype=torch.float32).contiguous()
-    else:
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        Xd = torch.as_tensor(np.asarray(X, dtype=np.float32), device=dev).contiguous()
-    if Xd.dim() != 2 or Xd.shape[0] < 1 or Xd.shape[1] < 1:
-        raise ValueError("X must be 2-D [n_samples, n_features] with at least one row and one column")
-    return Xd
 
 
 def _dbscan_pass(Xd, eps_list, min_samples, workspace_cap=None):
@@ -479,7 +458,7 @@ class DBSCAN:
     def fit(self, X, y=None, sample_weight=None):
         if sample_weight is not None:
             raise ValueError("sample_weight is not supported (the reference never passes it)")
-        Xd = _dbscan_device_x(X, self.device)
+        Xd = L.device_matrix(X, self.device)
         (_, labels, core, border), = _dbscan_pass(Xd, [self.eps], self.min_samples)
         self.labels_ = labels
         self.core_sample_indices_ = np.flatnonzero(core)
@@ -503,7 +482,7 @@ def dbscan_eps_sweep(X, eps_range=np.arange(3.0, 20.0, 1.0), min_samples=5, *, d
     its own, as the reference passes it; ``None`` when the radius has fewer than 2 clusters).  ``best_eps`` is
     the first radius with the highest silhouette, or the reference's default 10.0 when no radius qualifies."""
     from . import metrics as M
-    Xd = _dbscan_device_x(X, device)
+    Xd = L.device_matrix(X, device)
     eps_list = [float(e) for e in np.asarray(eps_range, dtype=np.float64).reshape(-1)]
     records = []
     best_eps, best_sil = 5.0, -1
@@ -527,9 +506,7 @@ _WARD_MAX_N = 32768
 
 
 def _ward_device_x(X, device):
-    Xd = _dbscan_device_x(X, device)
-    if not bool(torch.isfinite(Xd).all()):
-        raise ValueError("Input X contains NaN or infinity.")
+    Xd = L.device_matrix(X, device, finite=True)
     n = Xd.shape[0]
     if n < 2:
         raise ValueError(f"Found array with {n} sample(s) while a minimum of 2 is required by AgglomerativeClustering.")

@@ -3,8 +3,8 @@
 //
 // Neighbourhood pass (one pass over the distance tiles serves all E radii of a sweep):
 //   i ~ j  iff  max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) <= r_e        (everything float64 on the upcast float32 rows)
-// x_i.x_j comes from the fp64 MFMA (v_mfma_f64_16x16x4_f64) on 64 x 64 tiles staged through LDS as doubles; a tile
-// is 64 columns wide so one tile row is one word of the bit-packed adjacency adj[e][i][j / 64].  The expression
+// x_i.x_j comes from the fp64 MFMA tile of f64tile.hpp (both operands row images); a tile is 64 columns wide so one
+// tile row is one word of the bit-packed adjacency adj[e][i][j / 64].  The expression
 // (n_i + n_j) - 2 dot is symmetric in i and j bit for bit (the MFMA sums over k in the same order for (i, j) and
 // (j, i)), so the adjacency is symmetric.  A pair within 4 (d + 4) 2^-53 (n_i + n_j) of a threshold is counted as
 // borderline (another summation order could flip it); the count is reported, nothing else changes.
@@ -18,31 +18,21 @@
 #include <algorithm>
 #include <climits>
 
+#include "f64tile.hpp"
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
+using namespace f64tile;
 typedef unsigned long long u64;
 
-constexpr int kTile = 64;        // rows and columns of a block's distance tile (one adjacency word per row)
-constexpr int kKC = 32;          // K chunk staged per LDS fill
-constexpr int kLS = kKC + 2;     // LDS row stride in doubles: the 16 rows x 2 k of a half-wave's 8-byte reads
-                                 // fall on 32 distinct bank pairs (68 dwords = 4 mod 64)
 constexpr int kMaxRadii = 32;    // radii per launch (kernel argument block)
 
 struct Radii {
     double r[kMaxRadii];
 };
-
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // float64 squared row norms of the float32 rows: one wave per row, fixed order
 __global__ __launch_bounds__(256) void db_norms_kernel(const float* __restrict__ X, int64_t n, int d,
@@ -64,58 +54,35 @@ __global__ __launch_bounds__(256) void db_norms_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void db_neigh_kernel(const float* __restrict__ X, const double* __restrict__ norms,
                                                        int64_t n, int d, Radii R, int E, double tolc,
                                                        u64* __restrict__ adj, int64_t W, u64* __restrict__ border) {
-    __shared__ double As[kTile * kLS];
-    __shared__ double Bs[kTile * kLS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ double a_sh[RowImage::kDoubles];
+    __shared__ double b_sh[RowImage::kDoubles];
+    const RowImage As{a_sh}, Bs{b_sh};
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t i0 = (int64_t)blockIdx.y * kTile, j0 = (int64_t)blockIdx.x * kTile;
-    const int lr = lane & 15, lk = lane >> 4;
-    double4_t acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
-    // the next K chunk's 2 x 8 floats per thread are fetched into registers while the MFMAs of this one run
-    constexpr int kPer = kTile * kKC / 256;
-    float pa[kPer], pb[kPer];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int e = tid + u * 256, r = e / kKC, c = e - r * kKC;
-            const bool ck = k0 + c < d;      // zero fill: the K tail (d % 4 != 0) and the rows past n
-            pa[u] = (ck && i0 + r < n) ? X[(i0 + r) * d + k0 + c] : 0.f;
-            pb[u] = (ck && j0 + r < n) ? X[(j0 + r) * d + k0 + c] : 0.f;
-        }
-    };
-    fetch(0);
+    double4_t acc[4] = {};
+    Stage<RowImage, float> pa, pb;   // the next K chunk is fetched into registers while the MFMAs of this one run
+    pa.fetch(X, d, i0, n, 0, d);
+    pb.fetch(X, d, j0, n, 0, d);
     for (int k0 = 0; k0 < d; k0 += kKC) {
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int e = tid + u * 256, r = e / kKC, c = e - r * kKC;
-            As[r * kLS + c] = (double)pa[u];
-            Bs[r * kLS + c] = (double)pb[u];
-        }
+        pa.commit(As);
+        pb.commit(Bs);
         __syncthreads();
-        if (k0 + kKC < d) fetch(k0 + kKC);
-        const int kmax = min(kKC, (d - k0 + 3) & ~3);
-        for (int kk = 0; kk < kmax; kk += 4) {
-            // A: lane holds A[row lane & 15][k lane >> 4]; B: B[k lane >> 4][col lane & 15]
-            const double a = As[(wv * 16 + lr) * kLS + kk + lk];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const double b = Bs[(t * 16 + lr) * kLS + kk + lk];
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-            }
+        if (k0 + kKC < d) {
+            pa.fetch(X, d, i0, n, k0 + kKC, d);
+            pb.fetch(X, d, j0, n, k0 + kKC, d);
         }
+        mma_chunk(acc, As, Bs, k_steps(d - k0));
     }
-    // C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 * reg
     double d2[4][4], tol[4][4];
     bool valid[4][4], upper[4][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const int64_t gi = i0 + wv * 16 + lk + 4 * q;
+        const int64_t gi = i0 + acc_row(q);
         const double ni = gi < n ? norms[gi] : 0.0;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const int64_t gj = j0 + t * 16 + lr;
+            const int64_t gj = j0 + acc_col(t);
             const double nj = gj < n ? norms[gj] : 0.0;
             const double sn = ni + nj;
             d2[t][q] = fmax(0.0, sn - 2.0 * acc[t][q]);
@@ -135,7 +102,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int t = 0; t < 4; ++t) {
                 const double diff = d2[t][q] - r;
                 const u64 b = __ballot(valid[t][q] && d2[t][q] <= r);
-                // ballot bits [16 g, 16 g + 16) are row g + 4 q, columns 16 t .. 16 t + 15
+                // ballot bits [16 g, 16 g + 16) are row g + 4 q, columns 16 t .. 16 t + 15 (acc_row, acc_col)
                 word |= ((b >> (16 * (lane & 3))) & 0xffffull) << (16 * t);
                 nb += (upper[t][q] && fabs(diff) <= tol[t][q]) ? 1 : 0;
             }
@@ -143,7 +110,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             if (lane < 4 && gi < n) arow[(size_t)gi * (size_t)W + blockIdx.x] = word;
         }
         if (__ballot(nb > 0)) {   // rare: integer atomic, order-independent
-            const int tot = wave_sum_int(nb);
+            const int tot = wave_sum(nb);
             if (lane == 0) atomicAdd(&border[e], (u64)tot);
         }
     }
@@ -158,7 +125,7 @@ __global__ __launch_bounds__(256) void db_count_kernel(const u64* __restrict__ a
     const u64* a = adj + (size_t)row * (size_t)W;
     int c = 0;
     for (int64_t w = lane; w < W; w += 64) c += __popcll(a[w]);
-    c = wave_sum_int(c);
+    c = wave_sum(c);
     if (lane == 0) counts[row] = c;
 }
 
@@ -297,15 +264,15 @@ struct Layout {
 
 Layout layout(int64_t n, int E) {
     const size_t W = (size_t)(n + 63) / 64;
+    Carver c;
     Layout l;
-    size_t o = 0;
-    l.adj = o;      o += align256((size_t)E * (size_t)n * W * sizeof(u64));
-    l.norms = o;    o += align256((size_t)n * sizeof(double));
-    l.parent = o;   o += align256((size_t)n * sizeof(int32_t));
-    l.root = o;     o += align256((size_t)n * sizeof(int32_t));
-    l.cid = o;      o += align256((size_t)n * sizeof(int32_t));
-    l.corebits = o; o += align256(W * sizeof(u64));
-    l.total = o;
+    l.adj = c.take((size_t)E * (size_t)n * W * sizeof(u64));
+    l.norms = c.take((size_t)n * sizeof(double));
+    l.parent = c.take((size_t)n * sizeof(int32_t));
+    l.root = c.take((size_t)n * sizeof(int32_t));
+    l.cid = c.take((size_t)n * sizeof(int32_t));
+    l.corebits = c.take(W * sizeof(u64));
+    l.total = c.off;
     return l;
 }
 

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 namespace {
@@ -265,28 +266,59 @@ int launch_sums(hipStream_t s, const float* X, int64_t n, int d, const int32_t* 
     return HLMC_OK;
 }
 
-size_t counts_bytes(int k) { return ((size_t)k * sizeof(int32_t) + 255) / 256 * 256; }
+size_t counts_bytes(int k) { return align256((size_t)k * sizeof(int32_t)); }   // zeroed whole before the count
 
 constexpr int kCluWin = 96 * 1024 / sizeof(double);   // doubles of the clu_sums LDS label window
+
+struct SilLayout {
+    size_t S, counts, part, total;
+};
+
+SilLayout sil_layout(int64_t n, int k) {
+    Carver c;
+    SilLayout l;
+    l.S = c.take((size_t)n * k * sizeof(double));
+    l.counts = c.take((size_t)k * sizeof(int32_t));
+    l.part = c.pack(kSilFinalBlocks * sizeof(double));
+    l.total = c.off;
+    return l;
+}
+
+// the double arrays lie back to back; only counts is rounded up
+struct CluLayout {
+    size_t part, part2, cent, mean, counts, intra, total;
+};
+
+CluLayout clu_layout(int k, int d) {
+    Carver c;
+    CluLayout l;
+    l.part = c.pack((size_t)kCluBlocks * k * d * sizeof(double));
+    l.part2 = c.pack((size_t)kCluBlocks * k * 2 * sizeof(double));
+    l.cent = c.pack((size_t)k * d * sizeof(double));
+    l.mean = c.pack((size_t)d * sizeof(double));
+    l.counts = c.take((size_t)k * sizeof(int32_t));
+    l.intra = c.pack((size_t)k * sizeof(double));
+    l.total = c.off;
+    return l;
+}
 
 }  // namespace
 
 namespace metrics {
 
-size_t silhouette_workspace(int64_t n, int k) {
-    return ((size_t)n * k * sizeof(double) + 255) / 256 * 256 + counts_bytes(k) + kSilFinalBlocks * sizeof(double);
-}
+size_t silhouette_workspace(int64_t n, int k) { return sil_layout(n, k).total; }
 
 int silhouette(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels, int k, double* samples,
                double* score, void* ws, size_t ws_bytes) {
     HLMC_CHECK_ARG(X && labels && score && ws, "silhouette: NULL argument");
     HLMC_CHECK_ARG(n >= 2 && d >= 1 && d <= 128, "silhouette: need n >= 2 and 1 <= d <= 128 (row held in registers)");
     HLMC_CHECK_ARG(k >= 2 && k <= n - 1, "silhouette: number of labels must be in [2, n - 1] (sklearn)");
-    HLMC_CHECK_ARG(ws_bytes >= silhouette_workspace(n, k), "silhouette: workspace too small");
+    const SilLayout l = sil_layout(n, k);
+    HLMC_CHECK_ARG(ws_bytes >= l.total, "silhouette: workspace too small");
     char* w = static_cast<char*>(ws);
-    double* S = reinterpret_cast<double*>(w);
-    int32_t* counts = reinterpret_cast<int32_t*>(w + ((size_t)n * k * sizeof(double) + 255) / 256 * 256);
-    double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(counts) + counts_bytes(k));
+    double* S = reinterpret_cast<double*>(w + l.S);
+    int32_t* counts = reinterpret_cast<int32_t*>(w + l.counts);
+    double* part = reinterpret_cast<double*>(w + l.part);
     HLMC_HIP(hipMemsetAsync(counts, 0, counts_bytes(k), s));
     sil_count_kernel<<<(unsigned)std::min<int64_t>(1024, (n + 255) / 256), 256, 0, s>>>(labels, n, k, counts);
     HLMC_LAUNCHED();
@@ -301,10 +333,7 @@ int silhouette(hipStream_t s, const float* X, int64_t n, int d, const int32_t* l
     return HLMC_OK;
 }
 
-size_t cluster_scores_workspace(int k, int d) {
-    return (size_t)kCluBlocks * k * d * sizeof(double) + (size_t)kCluBlocks * k * 2 * sizeof(double) +
-           (size_t)k * d * sizeof(double) + (size_t)d * sizeof(double) + counts_bytes(k) + (size_t)k * sizeof(double);
-}
+size_t cluster_scores_workspace(int k, int d) { return clu_layout(k, d).total; }
 
 int cluster_scores(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels, int k, double* out2,
                    void* ws, size_t ws_bytes) {
@@ -312,13 +341,15 @@ int cluster_scores(hipStream_t s, const float* X, int64_t n, int d, const int32_
     HLMC_CHECK_ARG(n >= 2 && d >= 1 && d <= 4096, "cluster_scores: need n >= 2, 1 <= d <= 4096");
     HLMC_CHECK_ARG(k >= 2 && k < n, "cluster_scores: number of labels must be in [2, n - 1]");
     HLMC_CHECK_ARG(4 * 2 * (size_t)k * sizeof(double) <= 64 * 1024, "cluster_scores: k too large (<= 1024)");
-    HLMC_CHECK_ARG(ws_bytes >= cluster_scores_workspace(k, d), "cluster_scores: workspace too small");
-    double* part = static_cast<double*>(ws);
-    double* part2 = part + (size_t)kCluBlocks * k * d;
-    double* cent = part2 + (size_t)kCluBlocks * k * 2;
-    double* mean = cent + (size_t)k * d;
-    int32_t* counts = reinterpret_cast<int32_t*>(mean + d);
-    double* intra = reinterpret_cast<double*>(reinterpret_cast<char*>(counts) + counts_bytes(k));
+    const CluLayout l = clu_layout(k, d);
+    HLMC_CHECK_ARG(ws_bytes >= l.total, "cluster_scores: workspace too small");
+    char* w = static_cast<char*>(ws);
+    double* part = reinterpret_cast<double*>(w + l.part);
+    double* part2 = reinterpret_cast<double*>(w + l.part2);
+    double* cent = reinterpret_cast<double*>(w + l.cent);
+    double* mean = reinterpret_cast<double*>(w + l.mean);
+    int32_t* counts = reinterpret_cast<int32_t*>(w + l.counts);
+    double* intra = reinterpret_cast<double*>(w + l.intra);
     HLMC_HIP(hipMemsetAsync(counts, 0, counts_bytes(k), s));
     sil_count_kernel<<<(unsigned)std::min<int64_t>(1024, (n + 255) / 256), 256, 0, s>>>(labels, n, k, counts);
     HLMC_LAUNCHED();

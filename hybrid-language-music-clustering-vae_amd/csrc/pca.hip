@@ -4,17 +4,16 @@
 // cov: the column mean and the centred Gram matrix G = (X - m)^T (X - m), two passes over X.
 //   Pass 1: float64 column sums per row slab (4 row groups per block, each in row order, combined 0..3), the slabs
 //   summed in slab order, mean = sum / n.
-//   Pass 2: one block per (upper-triangle 64 x 64 feature-tile pair, row slab).  A chunk of 32 sample rows is read
-//   coalesced along the feature axis, centred in float64 ((double)x - mean; a row past the slab's end is 0, not
-//   -mean), staged in LDS as [sample][feature] doubles and fed to the MFMA with the sample index as K:
-//   A[feature][sample], the transpose of the DBSCAN tile.  The slab's partial tile goes to the workspace; a second
-//   kernel sums the slabs in slab order and writes G[i][j] and G[j][i] from the same value (of a diagonal tile only
-//   the entries i <= j are used), so G is symmetric bit for bit.
+//   Pass 2: one block per (upper-triangle 64 x 64 feature-tile pair, row slab) on the tile of f64tile.hpp, the sample
+//   index as K and both operands k-major images (X's rows are the inner axis), centred in float64 when they are
+//   stored ((double)x - mean; a row past the slab's end is 0, not -mean).  The slab's partial tile goes to the
+//   workspace; a second kernel sums the slabs in slab order and writes G[i][j] and G[j][i] from the same value (of a
+//   diagonal tile only the entries i <= j are used), so G is symmetric bit for bit.
 //   The slab length depends on n alone, no float atomics: the result is bit-identical from run to run.
 //
-// project: out = (A - a_off) B + o_off, A float32 [n][p], B float64 [p][q], accumulated in float64 on the MFMA and
-//   rounded once to float32; 64 x 64 output tiles, K walked in chunks of 32 with zero fill.  transform,
-//   inverse_transform and whitening are this one kernel with different B and offsets.
+// project: out = (A - a_off) B + o_off, A float32 [n][p] (row image), B float64 [p][q] (k-major image), accumulated
+//   in float64 on the MFMA and rounded once to float32.  transform, inverse_transform and whitening are this one
+//   kernel with different B and offsets.
 //
 // Rounding count, assuming the MFMA's 4-step inner sum rounds each product and each addition at most
 // once: a Gram entry takes one rounding per centred factor, one per product and n - 1 additions of nonzero terms (the
@@ -22,27 +21,19 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "f64tile.hpp"
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
+using namespace f64tile;   // kTile: features (cov) / rows and columns (project); kKC: sample rows / inner columns
 
-constexpr int kTile = 64;        // features (cov) / rows and columns (project) of a block's output tile
-constexpr int kKC = 32;          // K chunk staged per LDS fill (sample rows for cov, inner columns for project)
-// [k][64] operand images (cov's both operands, project's B): lane (lr = lane & 15, lk = lane >> 4) reads double
-// (kk + lk) * kLSF + 16 t + lr.  An 8-byte read is served per 32-lane half over 32 bank pairs, and a half holds
-// lk in {0, 1} (or {2, 3}) x 16 lr: kLSF = 16 mod 32 puts the two k rows on the two halves of the bank row.
-constexpr int kLSF = kTile + 16;
-// [row][k] operand image (project's A): lane reads double (16 w + lr) * kLSK + kk + lk, 34 lr + lk mod 32 = 2 lr + lk
-constexpr int kLSK = kKC + 2;
 constexpr int kSlabMin = 256;    // shortest row slab
 constexpr int kSlabsMax = 128;   // most row slabs (bounds the workspace at 128 partial Gram matrices)
 constexpr int64_t kMaxN = (int64_t)1 << 24;
 constexpr int kMaxD = 1024;
-
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // rows per slab: a function of n alone
 int64_t slab_len(int64_t n) {
@@ -62,10 +53,10 @@ Layout layout(int64_t n, int d) {
     l.slabs = (n + l.slab - 1) / l.slab;
     l.tiles = (d + kTile - 1) / kTile;
     l.pairs = l.tiles * (l.tiles + 1) / 2;
-    size_t o = 0;
-    l.colsum = o; o += align256((size_t)l.slabs * (size_t)d * sizeof(double));
-    l.part = o;   o += align256((size_t)l.slabs * (size_t)l.pairs * kTile * kTile * sizeof(double));
-    l.total = o;
+    Carver c;
+    l.colsum = c.take((size_t)l.slabs * (size_t)d * sizeof(double));
+    l.part = c.take((size_t)l.slabs * (size_t)l.pairs * kTile * kTile * sizeof(double));
+    l.total = c.off;
     return l;
 }
 
@@ -110,61 +101,37 @@ __device__ __forceinline__ void pair_tiles(int pair, int tiles, int& ti, int& tj
 __global__ __launch_bounds__(256) void pca_gram_kernel(const float* __restrict__ X, const double* __restrict__ mean,
                                                        int64_t n, int d, int64_t slab, int tiles, int pairs,
                                                        double* __restrict__ part) {
-    __shared__ double As[kKC * kLSF];
-    __shared__ double Bs[kKC * kLSF];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int lr = lane & 15, lk = lane >> 4;
+    __shared__ double a_sh[KImage::kDoubles];
+    __shared__ double b_sh[KImage::kDoubles];
     int ti, tj;
     pair_tiles(blockIdx.x, tiles, ti, tj);
-    const bool diag = ti == tj;
+    const bool diag = ti == tj;   // one image serves both operands: the second is neither fetched nor stored
+    const KImage As{a_sh}, Bs{diag ? a_sh : b_sh};
     const int64_t r0 = (int64_t)blockIdx.y * slab, r1 = min(n, r0 + slab);
-    // a thread stages column lane of both tiles, sample rows wv, wv + 4, ... of the chunk
-    const int ci = ti * kTile + lane, cj = tj * kTile + lane;
+    Stage<KImage, float> pa, pb;   // the next chunk is fetched into registers while the MFMAs of this one run
+    // the column of each tile that the thread stages, and its mean
+    const int ci = ti * kTile + pa.minor(), cj = tj * kTile + pb.minor();
     const double mi = ci < d ? mean[ci] : 0.0, mj = cj < d ? mean[cj] : 0.0;
-    double4_t acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
-    constexpr int kPer = kKC * kTile / 256;
-    float pa[kPer], pb[kPer];
-    auto fetch = [&](int64_t k0) {   // the next chunk into registers while the MFMAs of this one run
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int64_t r = k0 + wv + 4 * u;
-            const bool rk = r < r1;
-            pa[u] = (rk && ci < d) ? X[r * d + ci] : 0.f;
-            pb[u] = (rk && cj < d && !diag) ? X[r * d + cj] : 0.f;
-        }
-    };
-    fetch(r0);
-    const double* Bt = diag ? As : Bs;
+    double4_t acc[4] = {};
+    pa.fetch(X, d, r0, r1, ti * kTile, d);
+    if (!diag) pb.fetch(X, d, r0, r1, tj * kTile, d);
     for (int64_t k0 = r0; k0 < r1; k0 += kKC) {
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int r = wv + 4 * u;
-            const bool rk = k0 + r < r1;   // a row past the slab contributes 0, not -mean
-            As[r * kLSF + lane] = rk ? (double)pa[u] - mi : 0.0;
-            if (!diag) Bs[r * kLSF + lane] = rk ? (double)pb[u] - mj : 0.0;
-        }
+        // centred where it is stored; a row past the slab contributes 0, not -mean
+        pa.commit(As, [mi](double x) { return x - mi; });
+        if (!diag) pb.commit(Bs, [mj](double x) { return x - mj; });
         __syncthreads();
-        if (k0 + kKC < r1) fetch(k0 + kKC);
-        const int kmax = (int)min((int64_t)kKC, (r1 - k0 + 3) & ~(int64_t)3);
-        for (int kk = 0; kk < kmax; kk += 4) {
-            // A: lane holds A[feature lane & 15][sample lane >> 4]; B: B[sample lane >> 4][feature lane & 15]
-            const double a = As[(kk + lk) * kLSF + wv * 16 + lr];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const double b = Bt[(kk + lk) * kLSF + t * 16 + lr];
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-            }
+        if (k0 + kKC < r1) {
+            pa.fetch(X, d, k0 + kKC, r1, ti * kTile, d);
+            if (!diag) pb.fetch(X, d, k0 + kKC, r1, tj * kTile, d);
         }
+        mma_chunk(acc, As, Bs, k_steps(r1 - k0));
     }
-    // C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 * reg
     double* out = part + ((size_t)blockIdx.y * pairs + blockIdx.x) * (kTile * kTile);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) out[(wv * 16 + lk + 4 * q) * kTile + t * 16 + lr] = acc[t][q];
+        for (int t = 0; t < 4; ++t) out[acc_row(q) * kTile + acc_col(t)] = acc[t][q];
 }
 
 // G[i][j] = G[j][i] = sum over the slabs, in slab order, of the pair's partial tiles; one block per pair
@@ -189,59 +156,40 @@ __global__ __launch_bounds__(256) void pca_project_kernel(const float* __restric
                                                           const double* __restrict__ B, int q,
                                                           const double* __restrict__ a_off,
                                                           const double* __restrict__ o_off, float* __restrict__ out) {
-    __shared__ double As[kTile * kLSK];
-    __shared__ double Bs[kKC * kLSF];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int lr = lane & 15, lk = lane >> 4;
+    __shared__ double a_sh[RowImage::kDoubles];
+    __shared__ double b_sh[KImage::kDoubles];
+    const RowImage As{a_sh};
+    const KImage Bs{b_sh};
     const int64_t i0 = (int64_t)blockIdx.x * kTile;
     const int j0 = blockIdx.y * kTile;
-    double4_t acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
-    constexpr int kPer = kTile * kKC / 256;
-    // A: thread stages inner column tid & 31 of rows tid >> 5, + 8, ...; B: column lane of inner rows wv, wv + 4, ...
-    const int ac = tid & 31, ar = tid >> 5;
-    double pa[kPer], pb[kPer];
-    auto fetch = [&](int k0) {   // zero fill: the K tail, the rows past n, the columns past q
-        const bool ck = k0 + ac < p;
-        const double off = (ck && a_off) ? a_off[k0 + ac] : 0.0;
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int64_t r = i0 + ar + 8 * u;
-            pa[u] = (ck && r < n) ? (double)A[r * p + k0 + ac] - off : 0.0;
-            const int k = k0 + wv + 4 * u;
-            pb[u] = (k < p && j0 + lane < q) ? B[(size_t)k * q + j0 + lane] : 0.0;
-        }
+    double4_t acc[4] = {};
+    // the next chunk, and a_off of the thread's inner column of A, is fetched while the MFMAs of this one run
+    Stage<RowImage, float> pa;
+    Stage<KImage, double> pb;
+    double off;
+    auto fetch = [&](int k0) {
+        const int c = k0 + pa.minor();
+        off = (c < p && a_off) ? a_off[c] : 0.0;
+        pa.fetch(A, p, i0, n, k0, p);
+        pb.fetch(B, q, k0, p, j0, q);
     };
     fetch(0);
     for (int k0 = 0; k0 < p; k0 += kKC) {
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            As[(ar + 8 * u) * kLSK + ac] = pa[u];
-            Bs[(wv + 4 * u) * kLSF + lane] = pb[u];
-        }
+        pa.commit(As, [off](double x) { return x - off; });
+        pb.commit(Bs);
         __syncthreads();
         if (k0 + kKC < p) fetch(k0 + kKC);
-        const int kmax = min(kKC, (p - k0 + 3) & ~3);
-        for (int kk = 0; kk < kmax; kk += 4) {
-            const double a = As[(wv * 16 + lr) * kLSK + kk + lk];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const double b = Bs[(kk + lk) * kLSF + t * 16 + lr];
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
-            }
-        }
+        mma_chunk(acc, As, Bs, k_steps(p - k0));
     }
-    // C/D of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4 * reg
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const int j = j0 + t * 16 + lr;
+        const int j = j0 + acc_col(t);
         if (j >= q) continue;
         const double oo = o_off ? o_off[j] : 0.0;
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
-            const int64_t r = i0 + wv * 16 + lk + 4 * qq;
+            const int64_t r = i0 + acc_row(qq);
             if (r < n) out[r * q + j] = (float)(acc[t][qq] + oo);
         }
     }

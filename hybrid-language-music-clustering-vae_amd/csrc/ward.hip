@@ -13,15 +13,16 @@
 // ends the kernel with a non-zero status word.
 #include <climits>
 
+#include "f64tile.hpp"
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 namespace {
 
-constexpr int kTile = 64;        // rows and columns of a block's distance tile
-constexpr int kKC = 32;          // K chunk staged per LDS fill
-constexpr int kLS = kKC + 2;     // LDS row stride in doubles: the 16 rows of a half-wave's 8-byte reads fall on
-                                 // 32 distinct bank pairs (68 dwords = 4 mod 64), as in dbscan.hip
+using f64tile::kKC;
+using f64tile::kTile;
+using f64tile::RowImage;
 constexpr int kTS = kTile + 1;   // stride of the transposed-store staging tile (130 dwords = 2 mod 64)
 constexpr int64_t kMaxN = 32768; // D is 8 GiB at the cap; size[] fills 128 KB of LDS
 constexpr int kChainThreads = 1024;
@@ -30,41 +31,38 @@ constexpr int kWaves = kChainThreads / 64;
 constexpr int kStatusNoNeighbour = 1;   // a scan found nothing smaller than +inf: NaN (or +inf) in D
 constexpr int kStatusBound = 2;         // chain longer than n or more than 4 n scans
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 // One 64 x 64 tile of distances per block (256 threads, a 4 x 4 register block each: rows ty + 16 q, columns
-// tx + 16 t).  Blocks below the diagonal return at once.
+// tx + 16 t) from the two row images of f64tile.hpp, read here by plain loads.  Blocks below the diagonal return at
+// once.
 __global__ __launch_bounds__(256) void ward_pdist_kernel(const float* __restrict__ X, int64_t n, int d,
                                                          double* __restrict__ D) {
     if (blockIdx.x < blockIdx.y) return;
-    __shared__ double sh[2 * kTile * kLS];   // As | Bs, reused as the [64][kTS] staging tile (4160 <= 4352)
-    double* As = sh;
-    double* Bs = sh + kTile * kLS;
+    __shared__ double sh[2 * RowImage::kDoubles];   // As | Bs, reused as the [64][kTS] staging tile (4160 <= 4352)
+    const RowImage As{sh}, Bs{sh + RowImage::kDoubles};
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int64_t i0 = (int64_t)blockIdx.y * kTile, j0 = (int64_t)blockIdx.x * kTile;
-    double s[4][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) s[q][t] = 0.0;
-    constexpr int kPer = kTile * kKC / 256;
+    double s[4][4] = {};
+    // the next K chunk is fetched into registers while this one is summed; the rows past n are zero-filled and never
+    // stored
+    f64tile::Stage<RowImage, float> pa, pb;
+    pa.fetch(X, d, i0, n, 0, d);
+    pb.fetch(X, d, j0, n, 0, d);
     for (int k0 = 0; k0 < d; k0 += kKC) {
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int e = tid + u * 256, r = e / kKC, c = e - r * kKC;
-            const bool ck = k0 + c < d;      // zero fill: the K tail and the rows past n (never stored)
-            As[r * kLS + c] = (ck && i0 + r < n) ? (double)X[(i0 + r) * d + k0 + c] : 0.0;
-            Bs[r * kLS + c] = (ck && j0 + r < n) ? (double)X[(j0 + r) * d + k0 + c] : 0.0;
-        }
+        pa.commit(As);
+        pb.commit(Bs);
         __syncthreads();
+        if (k0 + kKC < d) {
+            pa.fetch(X, d, i0, n, k0 + kKC, d);
+            pb.fetch(X, d, j0, n, k0 + kKC, d);
+        }
         const int kmax = min(kKC, d - k0);
         for (int kk = 0; kk < kmax; ++kk) {   // sequential in k: the order of the sum is part of the result
             double a[4], b[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] = As[(ty + 16 * q) * kLS + kk];
+            for (int q = 0; q < 4; ++q) a[q] = As.el(ty + 16 * q, kk);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) b[t] = Bs[(tx + 16 * t) * kLS + kk];
+            for (int t = 0; t < 4; ++t) b[t] = Bs.el(tx + 16 * t, kk);
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -223,12 +221,12 @@ struct Layout {
 };
 
 Layout layout(int64_t n) {
+    Carver c;
     Layout l;
-    size_t o = 0;
-    l.D = o;      o += align256((size_t)n * (size_t)n * sizeof(double));
-    l.status = o; o += 256;
-    l.chain = o;  o += align256((size_t)n * sizeof(int32_t));
-    l.total = o;
+    l.D = c.take((size_t)n * (size_t)n * sizeof(double));   // first: callers pass the workspace itself as D
+    l.status = c.take(sizeof(int32_t));
+    l.chain = c.take((size_t)n * sizeof(int32_t));
+    l.total = c.off;
     return l;
 }
 

@@ -23,24 +23,6 @@ _MAX_FEATURES = 1024
 _MAX_SAMPLES = 1 << 24
 
 
-def _device_x(X, device):
-    """X as a contiguous float32 tensor on the device; shape and finiteness are checked where X lives, first."""
-    if torch.is_tensor(X):
-        X = X.detach()
-        dev = torch.device(device) if device is not None else (
-            X.device if X.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    else:
-        X = torch.from_numpy(np.ascontiguousarray(np.asarray(X, dtype=np.float32)))
-        dev = torch.device(device) if device is not None else None
-    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError("X must be 2-D [n_samples, n_features] with at least one row and one column")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("Input X contains NaN or infinity.")
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return X.to(device=dev, dtype=torch.float32).contiguous()
-
-
 def _project(A, B, a_off, o_off):
     """out [n][q] f32 = (A - a_off) B + o_off on the device; B [p][q], a_off [p], o_off [q]: host float64 or None."""
     n, p = A.shape
@@ -127,7 +109,7 @@ class PCA:
         if d > _MAX_FEATURES:
             raise ValueError(f"PCA: n_features={d} is above the supported {_MAX_FEATURES}")
         k = self._resolve_components(n, d)
-        Xd = _device_x(X, self.device)
+        Xd = L.device_matrix(X, self.device, finite=True)
         lib = L.lib()
         dev = Xd.device
         ws_bytes = int(lib.hlmc_pca_workspace(n, d))
@@ -174,14 +156,14 @@ class PCA:
         return self._forward(self._fit(X))
 
     def transform(self, X):
-        Xd = _device_x(X, self.device)
+        Xd = L.device_matrix(X, self.device, finite=True)
         if Xd.shape[1] != self.n_features_in_:
             raise ValueError(f"X has {Xd.shape[1]} features, but PCA is expecting {self.n_features_in_} features as "
                              f"input.")
         return self._forward(Xd)
 
     def inverse_transform(self, X):
-        Zd = _device_x(X, self.device)
+        Zd = L.device_matrix(X, self.device, finite=True)
         if Zd.shape[1] != self.n_components_:
             raise ValueError(f"X has {Zd.shape[1]} components, but PCA was fitted with {self.n_components_}")
         B = self._components64

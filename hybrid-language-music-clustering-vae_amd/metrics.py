@@ -29,17 +29,8 @@ def _encode(labels):
     return enc.astype(np.int32).reshape(-1), len(classes)
 
 
-def _device_x(X, device=None):
-    if torch.is_tensor(X):
-        dev = X.device if X.is_cuda else torch.device(device or "cuda")
-        return X.detach().to(device=dev, dtype=torch.float32).contiguous()
-    return torch.as_tensor(np.asarray(X, dtype=np.float32), device=device or "cuda").contiguous()
-
-
 def _prepare(X, labels):
-    x = _device_x(X)
-    if x.dim() != 2:
-        raise ValueError("X must be 2-D [n_samples, n_features]")
+    x = L.device_matrix(X)
     enc, k = _encode(labels)
     if enc.shape[0] != x.shape[0]:
         raise ValueError(f"X has {x.shape[0]} rows but labels has {enc.shape[0]} entries")
@@ -49,19 +40,24 @@ def _prepare(X, labels):
     return x, torch.from_numpy(enc).to(x.device), k
 
 
-def silhouette_samples(X, labels, *, metric="euclidean"):
-    """Per-sample silhouette coefficients (float64 tensor on the GPU), sklearn semantics."""
-    if metric != "euclidean":
-        raise ValueError("only metric='euclidean' (the reference's) is implemented")
+def _silhouette(X, labels, want_samples):
+    """(per-sample coefficients [n] or None, their mean [1]): float64 tensors on the GPU."""
     x, lab, k = _prepare(X, labels)
     n, d = x.shape
     lib = L.lib()
     ws = torch.empty(int(lib.hlmc_silhouette_workspace(n, k)), dtype=torch.uint8, device=x.device)
-    out = torch.empty(n, dtype=torch.float64, device=x.device)
+    out = torch.empty(n, dtype=torch.float64, device=x.device) if want_samples else None
     score = torch.empty(1, dtype=torch.float64, device=x.device)
-    L.check(lib.hlmc_silhouette(L.stream(), x.data_ptr(), n, d, lab.data_ptr(), k, out.data_ptr(), score.data_ptr(),
+    L.check(lib.hlmc_silhouette(L.stream(), x.data_ptr(), n, d, lab.data_ptr(), k, L.ptr(out), score.data_ptr(),
                                 ws.data_ptr(), ws.numel()), "hlmc_silhouette")
-    return out
+    return out, score
+
+
+def silhouette_samples(X, labels, *, metric="euclidean"):
+    """Per-sample silhouette coefficients (float64 tensor on the GPU), sklearn semantics."""
+    if metric != "euclidean":
+        raise ValueError("only metric='euclidean' (the reference's) is implemented")
+    return _silhouette(X, labels, True)[0]
 
 
 def silhouette_score(X, labels, *, metric="euclidean", sample_size=None, random_state=None):
@@ -75,14 +71,7 @@ def silhouette_score(X, labels, *, metric="euclidean", sample_size=None, random_
         lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
         X = X[torch.as_tensor(idx, device=X.device)] if torch.is_tensor(X) else np.asarray(X)[idx]
         labels = lab[idx]
-    x, lab, k = _prepare(X, labels)
-    n, d = x.shape
-    lib = L.lib()
-    ws = torch.empty(int(lib.hlmc_silhouette_workspace(n, k)), dtype=torch.uint8, device=x.device)
-    score = torch.empty(1, dtype=torch.float64, device=x.device)
-    L.check(lib.hlmc_silhouette(L.stream(), x.data_ptr(), n, d, lab.data_ptr(), k, None, score.data_ptr(),
-                                ws.data_ptr(), ws.numel()), "hlmc_silhouette")
-    return float(score.item())
+    return float(_silhouette(X, labels, False)[1].item())
 
 
 def _cluster_scores(X, labels):

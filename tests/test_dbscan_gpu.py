@@ -3,6 +3,7 @@ and to a live ``sklearn.cluster.DBSCAN`` (``algorithm='brute'`` where d <= 15), 
 the numpy checker's (tests/dbscan_check.py) and be 0 on every real-valued case, the exact-arithmetic cases (integer
 lattice, bridge point) must be equal although their ties count as borderline, and the eps sweep must agree with
 single fits and with the reference's search loop."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -11,6 +12,7 @@ import torch
 from sklearn.cluster import DBSCAN as SkDBSCAN
 
 import hlmc_amd
+from hlmc_amd import _lib as L
 from tests import dbscan_check as K
 
 pytestmark = pytest.mark.gpu
@@ -177,3 +179,39 @@ def test_two_runs_give_identical_bits(cuda):
     sweep = [hlmc_amd.dbscan_eps_sweep(X, [eps, 14.0, 19.5])[1] for _ in range(2)]
     for ra, rb in zip(*sweep):
         assert ra["labels"].tobytes() == rb["labels"].tobytes() and ra["silhouette"] == rb["silhouette"]
+
+
+def _neighbors_op(X, radii_sq, dev):
+    """hlmc_dbscan_neighbors on its own: (counts int32 [E][n], borderline pairs [E])."""
+    lib = L.lib()
+    n, d = X.shape
+    E = len(radii_sq)
+    Xd = torch.from_numpy(X).to(dev)
+    ws_bytes = int(lib.hlmc_dbscan_workspace(n, E))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    counts = torch.full((E, n), -1, dtype=torch.int32, device=dev)
+    border = torch.full((E,), -1, dtype=torch.int64, device=dev)
+    r = (C.c_double * E)(*radii_sq)
+    L.check(lib.hlmc_dbscan_neighbors(L.stream(), Xd.data_ptr(), n, d, r, E, counts.data_ptr(), border.data_ptr(),
+                                      ws.data_ptr(), ws_bytes), "hlmc_dbscan_neighbors")
+    return counts.cpu().numpy(), border.cpu().numpy()
+
+
+# the tile edge on both grid axes x the K tail, chunk + 1 and several chunks + 2; one case with all 32 radii
+NEIGHBOR_SHAPES = [(n, d, None) for n in (1, 63, 64, 65, 129) for d in (1, 3, 4, 5, 33, 130)] + [(65, 5, 32)]
+
+
+@pytest.mark.parametrize("n,d,E", NEIGHBOR_SHAPES)
+def test_neighbors_op_counts_and_ties_are_exact(cuda, n, d, E):
+    """Integer-valued rows: every product and sum is exact in float64 in any order, so the op's neighbour counts and
+    borderline-pair counts (here: the exact ties |x_i - x_j|^2 == r) equal the numpy checker's, no tolerance.  Radii:
+    a tie value, a value no distance takes, a mid-range one."""
+    X = np.random.default_rng(1000 * n + d).integers(0, 4, (n, d)).astype(np.float32)
+    radii = [1.0, 2.5, 0.75 * d] if E is None else [0.5 * (e + 1) for e in range(E)]
+    counts, border = _neighbors_op(X, radii, cuda)
+    d2, norms = K.sq_distances(X)
+    tol = (4.0 * (d + 4) * 2.0 ** -53) * (norms[:, None] + norms[None, :])    # dbscan_check.neighbourhoods
+    for e, r in enumerate(radii):
+        assert np.array_equal(counts[e], (d2 <= r).sum(axis=1)), (n, d, r)
+        assert int(border[e]) == int(np.triu(np.abs(d2 - r) <= tol, k=1).sum()), (n, d, r)
+        assert (int(counts[e].sum()) - n) % 2 == 0, (n, d, r)     # every pair is seen from both sides

@@ -153,6 +153,35 @@ def test_kmeans_rejects_non_finite_and_misshapen_input():
         km.predict(X[:, :4])
 
 
+def test_input_gate_checks_the_float32_values():
+    """A float64 tensor holding a finite value above float32's range becomes infinity in the float32 matrix the
+    kernels read, so every estimator that asks for finite input rejects it (on CPU tensors: no device is touched);
+    the gate that does not ask (DBSCAN, the metrics) passes it through as infinity."""
+    import numpy as np
+    import torch
+    import hlmc_amd
+    X = torch.from_numpy(np.random.default_rng(1).normal(0, 1, (50, 5)))     # float64
+    ok = L.device_matrix(X, "cpu", finite=True)
+    assert ok.dtype == torch.float32 and ok.is_contiguous() and torch.equal(ok, X.to(torch.float32))
+    for big in (1e300, -1e300, 3.5e38):
+        Xb = X.clone()
+        Xb[7, 3] = big
+        assert bool(torch.isfinite(Xb).all())
+        with pytest.raises(ValueError, match="NaN or infinity"):
+            L.device_matrix(Xb, "cpu", finite=True)
+        km = hlmc_amd.KMeans(2, random_state=0, device="cpu")
+        km.cluster_centers_ = X[:2].numpy().astype(np.float32)
+        with pytest.raises(ValueError, match="NaN or infinity"):
+            km.fit(Xb)
+        with pytest.raises(ValueError, match="NaN or infinity"):
+            km.predict(Xb)
+        with pytest.raises(ValueError, match="NaN or infinity"):
+            hlmc_amd.AgglomerativeClustering(n_clusters=2, device="cpu").fit(Xb)
+        with pytest.raises(ValueError, match="NaN or infinity"):
+            hlmc_amd.PCA(2, device="cpu").fit(Xb)
+        assert not bool(torch.isfinite(L.device_matrix(Xb, "cpu")).all())
+
+
 def test_inertia_and_rowdist_reject_bad_arguments():
     base = dict(X=ONE, n=1000, d=16, C=ONE, k=5, labels=ONE, R=3, out=ONE, tmp=ONE)
     sizes = [(dict(n=0), b"sizes"), (dict(n=-1), b"sizes"), (dict(d=0), b"sizes"), (dict(d=-4), b"sizes")]
