@@ -11,6 +11,7 @@ Drop-in surface (reference names):
   AgglomerativeClustering, agglomerative_k_sweep   (sklearn's Ward clustering and its k sweep, same script)
   PCA, pca_kmeans_baseline                     (sklearn PCA and the "PCA + KMeans" rows of src/Simple_VAE.py and
                                                 src/Conditional_VAE.py)
+  TSNE                                         (sklearn t-SNE, the last step of all three scripts, exact repulsion)
   metrics.silhouette_score / davies_bouldin_score / calinski_harabasz_score / adjusted_rand_score /
   normalized_mutual_info_score / calculate_purity   (the sklearn.metrics evaluation calls)
   Adam                                         (torch.optim.Adam of the train loops)
@@ -26,6 +27,8 @@ from .features import (SPECTRAL_FEATURES, StandardScaler, chroma_stft, extract_m
                        spectral_centroid, spectral_rolloff, spectral_stats, zero_crossing_rate)
 from .decomposition import PCA, pca_kmeans_baseline
 from . import decomposition
+from .manifold import TSNE
+from . import manifold
 from . import metrics
 from . import preprocess
 from .losses import cvae_loss_function, loss_function, vae_loss
@@ -37,5 +40,5 @@ from . import pipeline
 __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_function", "vae_loss", "melspectrogram",
            "power_to_db", "mfcc", "extract_mel_spectrogram", "mean_std_pool", "mel_filterbank", "StandardScaler",
            "KMeans", "DBSCAN", "dbscan_eps_sweep", "AgglomerativeClustering", "agglomerative_k_sweep",
-           "PCA", "pca_kmeans_baseline",
+           "PCA", "pca_kmeans_baseline", "TSNE",
            "Adam", "Trainer", "GraphedStep", "metrics"]

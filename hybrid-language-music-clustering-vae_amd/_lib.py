@@ -115,6 +115,12 @@ _SIGS = {
     "hlmc_pca_workspace": (c_i64, [c_i64, c_int]),
     "hlmc_pca_cov": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64]),
     "hlmc_pca_project": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "hlmc_tsne_workspace": (c_i64, [c_i64, c_int, c_int]),
+    "hlmc_tsne_knn": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_tsne_affinities": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_tsne_gradient": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f64, c_vp, c_vp, c_int, c_vp, c_i64]),
+    "hlmc_tsne_run": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_f64, c_f64, c_f64, c_int, c_vp, c_vp,
+                              c_i64]),
     "hlmc_op_conv_s2": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_op_subpixel": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_op_wgrad_s2": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_i64]),

@@ -477,6 +477,32 @@ int hlmc_pca_project(void* stream, const float* A, int64_t n, int p, const doubl
     return pca::project(S(stream), A, n, p, B, q, a_off, o_off, out);
 }
 
+// ------------------------------------------------------------------------------------ t-SNE
+static size_t ws_size(int64_t b) { return b < 0 ? 0 : (size_t)b; }
+int64_t hlmc_tsne_workspace(int64_t n, int d, int k) { return (int64_t)tsne::workspace(n, d, k); }
+int hlmc_tsne_knn(void* stream, const float* X, int64_t n, int d, int k, int32_t* nbr_idx, double* nbr_d2, void* ws,
+                  int64_t ws_bytes) {
+    return tsne::knn(S(stream), X, n, d, k, nbr_idx, nbr_d2, ws, ws_size(ws_bytes));
+}
+int hlmc_tsne_affinities(void* stream, const int32_t* nbr_idx, const double* nbr_d2, int64_t n, int k,
+                         double perplexity, double* beta, double* cond_p, int64_t* indptr, int32_t* indices,
+                         float* values, void* ws, int64_t ws_bytes) {
+    return tsne::affinities(S(stream), nbr_idx, nbr_d2, n, k, perplexity, beta, cond_p, indptr, indices, values, ws,
+                            ws_size(ws_bytes));
+}
+int hlmc_tsne_gradient(void* stream, const float* Y, int64_t n, const int64_t* indptr, const int32_t* indices,
+                       const float* values, double exaggeration, float* grad, double* stats, int want_stats, void* ws,
+                       int64_t ws_bytes) {
+    return tsne::gradient(S(stream), Y, n, indptr, indices, values, exaggeration, grad, stats, want_stats, ws,
+                          ws_size(ws_bytes));
+}
+int hlmc_tsne_run(void* stream, float* Y, float* update, float* gains, int64_t n, const int64_t* indptr,
+                  const int32_t* indices, const float* values, double exaggeration, double momentum,
+                  double learning_rate, int n_iter, double* stats, void* ws, int64_t ws_bytes) {
+    return tsne::run(S(stream), Y, update, gains, n, indptr, indices, values, exaggeration, momentum, learning_rate,
+                     n_iter, stats, ws, ws_size(ws_bytes));
+}
+
 // ------------------------------------------------------------------------------------ op-level entries
 // Individual GEMM-family kernels (the building blocks of hlmc_net_*), exposed for testing and reuse.
 #define DT_DISPATCH(dtype, CALL_F32, CALL_BF16) ((dtype) == HLMC_BF16 ? (CALL_BF16) : (CALL_F32))

@@ -119,4 +119,21 @@ int project(hipStream_t s, const float* A, int64_t n, int p, const double* B, in
             const double* o_off, float* out);
 }  // namespace pca
 
+// t-SNE (tsne.hip): kNN on the fp64 MFMA, sklearn's perplexity search and the symmetrised CSR affinities, the exact
+// all-pairs gradient of the Barnes-Hut objective, and sklearn's gradient-descent iterations, all on the stream.
+namespace tsne {
+size_t workspace(int64_t n, int d, int k);
+int knn(hipStream_t s, const float* X, int64_t n, int d, int k, int32_t* nbr_idx, double* nbr_d2, void* ws,
+        size_t ws_bytes);
+int affinities(hipStream_t s, const int32_t* nbr_idx, const double* nbr_d2, int64_t n, int k, double perplexity,
+               double* beta, double* cond_p, int64_t* indptr, int32_t* indices, float* values, void* ws,
+               size_t ws_bytes);
+int gradient(hipStream_t s, const float* Y, int64_t n, const int64_t* indptr, const int32_t* indices,
+             const float* values, double exaggeration, float* grad, double* stats, int want_stats, void* ws,
+             size_t ws_bytes);
+int run(hipStream_t s, float* Y, float* update, float* gains, int64_t n, const int64_t* indptr,
+        const int32_t* indices, const float* values, double exaggeration, double momentum, double learning_rate,
+        int n_iter, double* stats, void* ws, size_t ws_bytes);
+}  // namespace tsne
+
 }  // namespace hlmc

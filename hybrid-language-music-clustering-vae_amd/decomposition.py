@@ -71,7 +71,7 @@ class PCA:
     components are kept privately and used by ``transform`` / ``inverse_transform``, which return device tensors.
 
     Out of scope: ``process_group=`` (a row-sharded Gram matrix), float64 input (it is converted to float32, as the
-    other estimators do), more than 1024 features (the reference itself declines PCA on raw mel) and t-SNE.
+    other estimators do), more than 1024 features (the reference itself declines PCA on raw mel).
     """
 
     def __init__(self, n_components=None, *, whiten=False, svd_solver="auto", random_state=None, device=None):

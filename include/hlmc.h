@@ -406,6 +406,65 @@ int hlmc_pca_cov(void* stream, const float* X, int64_t n, int d, double* mean, d
 int hlmc_pca_project(void* stream, const float* A, int64_t n, int p, const double* B, int q, const double* a_off,
                      const double* o_off, float* out);
 
+/* ---- t-SNE ----------------------------------------------------------------------------------------------------------
+ * sklearn.manifold.TSNE(n_components=2, random_state=42[, perplexity=30]).fit_transform(latents) at
+ * src/Simple_VAE.py:302-303, src/Convolutional_VAE.py:468-469 and src/Conditional_VAE.py:515-517: the objective of
+ * sklearn 1.7's method='barnes_hut' (sparse kNN affinities P, Student-t Q with one degree of freedom) with the
+ * repulsive sum and Z taken over ALL pairs -- sklearn's angle = 0 -- in a fixed order.  No float atomics: two runs give
+ * the same bits.  2 <= n <= 131072, 1 <= d <= 4096, 1 <= k <= min(512, n - 1); sklearn's k is
+ * min(n - 1, int(3 perplexity + 1)).  One workspace of hlmc_tsne_workspace(n, d, k) bytes serves all four calls; the
+ * gradient's part comes first and depends on n alone, so hlmc_tsne_gradient / hlmc_tsne_run accept the size of any
+ * (d, k) of the same n.  No call synchronises with the host.
+ *
+ * hlmc_tsne_knn: nbr_idx [n][k] int32 and nbr_d2 [n][k] float64, the k nearest OTHER rows of each row of X [n][d] f32,
+ * ascending by squared distance, equal distances by ascending index.  The distance is
+ * max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) in float64 (the dot product on the fp64 MFMA),
+ * |d2' - d2| <= 1.01 (d + 4) 2^-52 (|x_i|^2 + |x_j|^2) (oracle/kmeans_oracle.py sqdist_bound without its float32 term).
+ *
+ * hlmc_tsne_affinities: sklearn's _binary_search_perplexity per row in float64 on (double)(float)nbr_d2 (start beta = 1,
+ * double / halve while a bound is infinite, <= 100 steps, |H - log((float)perplexity)| <= 1e-5, a zero sum becomes
+ * (double)1e-8f): beta [n] float64 and cond_p [n][k] float64 in the neighbours' order.  A row's sums are taken by one wave: lane
+ * l adds its neighbours l, l + 64, ... in that order, the lanes are combined by the xor butterfly 32, 16, .., 1.  Then
+ * (P + P^T) / max(total, 2^-52) over the union pattern, without the entries whose sum is exactly 0 (an underflowed
+ * exp; scipy's P + P.T drops them too), as a CSR matrix: indptr [n + 1] int64, indices int32 ascending
+ * within each row, values float32; indices and values need room for 2 n k entries, indptr[n] are used.  Entry (i, j)
+ * and entry (j, i) hold the same bits.  The total is added per row in column order, the rows' sums by
+ * "thread t adds rows t, t + 256, ..., then the tree 128, 64, .., 1".
+ *
+ * hlmc_tsne_gradient: grad [n][2] f32 = 4 (exaggeration sum_j p_ij q_ij (y_i - y_j) - sum_{j != i} q_ij^2 (y_i - y_j) / Z),
+ * q_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} q_ij: what sklearn's _kl_divergence_bh returns at angle = 0 for
+ * P scaled by `exaggeration` (P is not rescaled in memory).  Y [n][2] f32.  stats [3] float64 (device):
+ * stats[0] = Z always; with want_stats != 0 also stats[1] = sum over the stored entries of
+ * p log(max(p, t) / max(q / Z, t)) with p = exaggeration * value and t = float32's smallest normal (sklearn's error
+ * term), and stats[2] = |grad|_2 of the float32 gradient.
+ * Repulsion: rows in blocks of 256 (one per thread), columns in S = ceil(n / L) slabs of
+ * L = max(256, ceil(n / 64) rounded up to a multiple of 256) columns; the pair arithmetic is float32 without FMA
+ * (dx = y_i0 - y_j0, dy likewise, q = rcp(1 + (dx dx + dy dy)), q q dx), every term is widened and added in float64 in
+ * column order, the slabs' partials are added in slab order.  Attraction: one wave per row in float64, lane l takes the
+ * stored entries l, l + 64, ..., then the xor butterfly.  Workspace, gradient part:
+ *   [part:    float64 [S][3][n]: slab s's sums for row i, component 0 / 1 the repulsive force, 2 the sum of q]
+ *   [rep:     float64 [3][n]: part[0] + part[1] + ... + part[S-1] in that order]
+ *   [rowstat: float64 [2][n]: the rows' error terms | squared gradient norms]
+ *   [grad:    float32 [n][2]: the gradient of hlmc_tsne_run's last iteration]
+ * each rounded up to 256 bytes.
+ *
+ * hlmc_tsne_run: n_iter iterations of sklearn's _gradient_descent on (Y, update, gains), all [n][2] f32, in float32
+ * without FMA: g = the gradient at Y; gains += 0.2 where update * g < 0, else gains *= 0.8; gains = max(gains, 0.01);
+ * update = momentum * update - learning_rate * (g * gains); Y += update.  stats as above, of the LAST iteration's
+ * gradient (taken at the Y before its update, as sklearn's error and gradient norm are). */
+int64_t hlmc_tsne_workspace(int64_t n, int d, int k);   /* bytes; 0 when a size is out of range */
+int hlmc_tsne_knn(void* stream, const float* X, int64_t n, int d, int k, int32_t* nbr_idx, double* nbr_d2, void* ws,
+                  int64_t ws_bytes);
+int hlmc_tsne_affinities(void* stream, const int32_t* nbr_idx, const double* nbr_d2, int64_t n, int k,
+                         double perplexity, double* beta, double* cond_p, int64_t* indptr, int32_t* indices,
+                         float* values, void* ws, int64_t ws_bytes);
+int hlmc_tsne_gradient(void* stream, const float* Y, int64_t n, const int64_t* indptr, const int32_t* indices,
+                       const float* values, double exaggeration, float* grad, double* stats, int want_stats, void* ws,
+                       int64_t ws_bytes);
+int hlmc_tsne_run(void* stream, float* Y, float* update, float* gains, int64_t n, const int64_t* indptr,
+                  const int32_t* indices, const float* values, double exaggeration, double momentum,
+                  double learning_rate, int n_iter, double* stats, void* ws, int64_t ws_bytes);
+
 
 /* ============================================================== op-level entry points
  * The kernels hlmc_net_* is built from, on NHWC activations (dtype HLMC_F32 / HLMC_BF16 for x, y, packed
