@@ -27,6 +27,7 @@ _SIGS = {
     "hlmc_last_error": (c_char_p, []),
     "hlmc_device_status": (c_int, [c_int]),
     "hlmc_test_bn_fused": (c_int, [c_i64, c_int]),
+    "hlmc_test_stft_grid": (c_int, [c_int]),
     "hlmc_mel_plan_create": (c_int, [c_int, c_int, c_int, c_int, c_f64, c_f64, P_vp]),
     "hlmc_mel_plan_destroy": (c_int, [c_vp]),
     "hlmc_mel_filterbank": (c_int, [c_vp, c_vp]),

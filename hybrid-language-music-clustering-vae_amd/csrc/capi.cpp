@@ -100,6 +100,7 @@ int hlmc_test_bn_fused(int64_t max_elems, int spin_max) {
     ops::test_bn_fused(max_elems, spin_max);
     return HLMC_OK;
 }
+int hlmc_test_stft_grid(int blocks) { return feat::test_stft_grid(blocks); }
 
 // ------------------------------------------------------------------------------------ features
 int hlmc_mel_plan_create(int sr, int n_fft, int hop, int n_mels, double fmin, double fmax, hlmc_mel_plan** out) {

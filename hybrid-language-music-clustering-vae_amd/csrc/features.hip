@@ -7,6 +7,7 @@
 // register-resident radix-16/16/4 Stockham FFT, and split back into the 1025 real-FFT bins.  Window / twiddle tables are built on the host in double precision.  The Slaney filterbank is
 // banded (each filter spans 4..53 bins) and stored as (first bin, count, weights) per mel band.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -68,7 +69,11 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
 constexpr int kWaves = 4;      // frames in flight per workgroup
 constexpr int kFpw = 4;        // frames per wave
 constexpr int kFpb = kWaves * kFpw;
-constexpr int kPwRow = kFFT + 4;    // power row (floats, 16-byte aligned)
+// Power row of one wave (floats, 16-byte aligned): bins 0..1024, then 7 floats of zero padding.  A mel band reads
+// whole 8-bin steps from its first non-zero bin rounded down to a multiple of 4, so its last step can reach bin
+// h + 7 <= 1031 past its last non-zero bin h <= 1024 (plan_create checks every band against kPwRow).  The padding
+// is zeroed by the block itself: the weights there are 0, and 0 * (a stale NaN or Inf) would be NaN.
+constexpr int kPwRow = kFFT + 8;
 constexpr int kTwB = 15 * 64;       // W1024^{p k1}, k1 = 1..15
 constexpr int kTwC = 5 * 64;        // radix-2 stage twiddles, lane bits 1..5
 constexpr int kMelLanes = 64;  // band pairs (n_mels <= 128)
@@ -363,8 +368,9 @@ __device__ __forceinline__ void stft_mel_body(const float* __restrict__ pcm, int
                                                        unsigned* __restrict__ clip_max, unsigned* __restrict__ clip_min,
                                                        double bin_hz, double roll, double* __restrict__ sout,
                                                        PipArgs pa) {
-    // LDS: FFT twiddles + one power row per wave (27 KB static); dynamic: band info, the chunk-transposed
-    // filterbank (kWL, 16 KB at n_mels = 128) and the mel staging rows: 52 KB in all, 3 blocks per CU.
+    // LDS: FFT twiddles + one power row per wave (kPwRow floats: 1025 bins + zero padding; 27 KB static); dynamic:
+    // band info, the chunk-transposed filterbank (kWL, 16 KB at n_mels = 128) and the mel staging rows: 52 KB in
+    // all, 3 blocks per CU.
     __shared__ float2 stw[kTwB + kTwC];
     __shared__ __align__(16) float pwb[kWaves][kPwRow];
     extern __shared__ int4 sbl[];
@@ -382,8 +388,8 @@ __device__ __forceinline__ void stft_mel_body(const float* __restrict__ pcm, int
     const int hi = (int)((int64_t)nitems * (xcd + 1) / 8);
     int it = (int)((int64_t)nitems * xcd / 8) + (int)(blockIdx.x >> 3);
     // raw sample pairs (x[2n], x[2n+1]) of frame t: n = lane + 64 r, through a buffer descriptor over the clip
-    // whose range check returns 0 outside it (center padding; negative offsets wrap past the range).  With an
-    // even clip length and hop a pair never straddles the clip's end, so one 8-byte load per pair.
+    // whose range check returns 0 outside it (center padding; negative offsets wrap past the range, per 4-byte
+    // load).  With an even clip length and hop a pair never straddles the clip's ends, so one 8-byte load per pair.
     // kPairs (launch-time choice, not a runtime branch): every fetch issues the same number of loads on every path,
     // so the compiler's wait counts at the frame loop's merge points stay exact (a conditional fetch made it wait
     // for the next frame's loads before using the current frame's, exposing their latency every frame)
@@ -397,11 +403,18 @@ __device__ __forceinline__ void stft_mel_body(const float* __restrict__ pcm, int
                 v[r] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, 4 * (start + 2 * (ln + 64 * r)), 0, 0));
             }
         } else {
+            // Two 4-byte loads per pair that must stay two: with an odd hop a pair can straddle the clip's START
+            // (x[-1], x[0]: byte offsets -4 and 0).  The compiler fused adjacent loads into one 8-byte load at offset
+            // -4, and the range check then dropped x[0] with x[-1] (the second word's offset does not wrap back to
+            // 0); frame 1 of every clip lost its first sample at hop 441.  The second word's distance is opaque, so
+            // the loads cannot be proven adjacent.
+            int word = 4;
+            asm volatile("" : "+v"(word));
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int i0 = start + 2 * (ln + 64 * r);
                 v[r].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, 4 * i0, 0, 0));
-                v[r].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, 4 * i0 + 4, 0, 0));
+                v[r].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, 4 * i0 + word, 0, 0));
             }
         }
     };
@@ -414,6 +427,7 @@ __device__ __forceinline__ void stft_mel_body(const float* __restrict__ pcm, int
     }
     for (int i = threadIdx.x; i < kTwB + kTwC; i += 256) stw[i] = tw[i];
     if constexpr (kMode == 0) {
+        if (lane < kPwRow - (kFFT + 1)) pwb[wave][kFFT + 1 + lane] = 0.f;  // row padding (no frame writes it)
         for (int l = threadIdx.x; l < kMelLanes; l += 256) sbl[l] = reinterpret_cast<const int4*>(band)[l];
         if constexpr (kWL)
             for (int i = threadIdx.x; i < nnz / 4; i += 256) swt[i] = gw4[i];
@@ -961,6 +975,13 @@ int plan_create(int sr, int n_fft, int hop, int n_mels, double fmin, double fmax
         cnt[m] = ((span + 7) / 8) * 2;  // chunks of 4, even
         p->max_band = std::max(p->max_band, h - l + 1);
     }
+    // the kernel reads 4 cnt[m] floats of its wave's power row from lo[m] on, unchecked: every band must end inside
+    // the row (bins past 1024 are the row's zero padding)
+    for (int m = 0; m < n_mels; ++m)
+        if (lo[m] + 4 * cnt[m] > kPwRow) {
+            delete p;
+            HLMC_CHECK_ARG(false, "mel band reads past the kernel's power row");
+        }
     std::vector<int> band(4 * kMelLanes, 0);
     int C = 0;
     for (int l = 0; l < npairs; ++l) {
@@ -1014,9 +1035,18 @@ int64_t workspace(const MelPlanImpl* p, int64_t B, int64_t n) {
 }
 
 // Persistent grid of the STFT kernels: resident blocks over all CUs (a multiple of 8, one share per XCD), at most
-// one per item rounded up to the XCD count.
+// one per item rounded up to the XCD count.  The test hook replaces it by a given multiple of 8 (any such grid
+// computes the same values: fewer blocks walk more items each), so small batches reach the multi-item walk.
+static std::atomic<int> g_test_stft_grid{0};  // test hook (hlmc_test_stft_grid): 0, or the grid to launch
+int test_stft_grid(int blocks) {
+    HLMC_CHECK_ARG(blocks >= 0 && blocks % 8 == 0, "blocks must be 0 or a positive multiple of 8");
+    g_test_stft_grid.store(blocks);
+    return HLMC_OK;
+}
+
 template <typename K>
 static unsigned stft_grid(K kernel, size_t dyn, int64_t nitems) {
+    if (const int forced = g_test_stft_grid.load()) return (unsigned)forced;
     int dev = 0, cus = 0, occ = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, dyn) != hipSuccess || occ < 1) occ = 1;

@@ -29,6 +29,7 @@ struct MelPlanImpl {
 namespace feat {
 int plan_create(int sr, int n_fft, int hop, int n_mels, double fmin, double fmax, MelPlanImpl** out);
 void plan_destroy(MelPlanImpl* p);
+int test_stft_grid(int blocks);  // test hook: 0 = default grid, else that many blocks (a multiple of 8)
 int64_t frames(const MelPlanImpl* p, int64_t n);
 int64_t workspace(const MelPlanImpl* p, int64_t B, int64_t n);
 int melspectrogram(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t B, int64_t n, float* out, void* ws);

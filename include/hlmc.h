@@ -39,6 +39,11 @@ int hlmc_device_status(int clear);
 /* test hook: largest R * C taking the one-launch BatchNorm backward (-1: the default 2^22; 0: two passes everywhere)
  * and the arrival spin's poll bound (-1: the default).  Not for production use. */
 int hlmc_test_bn_fused(int64_t max_elems, int spin_max);
+/* test hook: the persistent grid of the STFT kernels (mel, spectral shape, piptrack).  0 restores the default (resident
+ * blocks, at most one per item); a positive multiple of 8 launches exactly that many blocks, so that a small batch
+ * walks several items per block.  Any such grid computes the same values.  Anything else returns HLMC_EINVAL.  Not for
+ * production use. */
+int hlmc_test_stft_grid(int blocks);
 
 /* ============================================================== features
  * Replaces librosa.feature.melspectrogram + librosa.power_to_db at
