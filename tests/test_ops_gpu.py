@@ -1,7 +1,20 @@
 """Op-level parity of the HIP GEMM families vs torch CPU float64 references (NHWC <-> NCHW).
 
 fp32 path (exact-fp32 MFMA): relative L2 error <= 1e-5.  bf16 path: operands rounded to bf16 on
-both sides, fp32 accumulation; relative L2 error <= 1e-2 (bf16 output rounding ~4e-3)."""
+both sides, fp32 accumulation; relative L2 error <= 1e-2 (bf16 output rounding ~4e-3).
+
+Beside each norm, every element of the GEMM and conv outputs is held to tests/exact_cases.py assert_elementwise:
+|got - ref| <= u_out |ref| + (k_terms + 16) 2^-23 absref (k_terms: 9 Ci convs, K linear, B Hl Wl weight gradients, Mb
+linear_wgrad).  Largest error / bound per family on an MI355X (all shapes of this file; bf16 inputs | fp32 inputs):
+    conv_s2            0.974 (B = 256, 64 x 64, 32 -> 64)  | 0.003       subpixel          0.975 | 0.007
+    halo plain edge    0.966                               |             halo_fwd y        0.973 (bn_in, B = 257)
+    linear             0.987 (256, 74, 2304)               | 0.025       linear relu mask  0.923 | 0.009
+    conv_c1_s2         0.995 (16, 128, 128)                | 0.093       convT_c1          0.006 | 0.006
+    wgrad_s2 (f32 out) 0.042                               | 0.083       linear_wgrad      0.034 | 0.086
+    wgrad_c1 (f32 out) 0.001                               | 0.001
+A bf16 output sits just under 1 because its half-ulp rounding term is tight (the CPU float32 stand-in reaches 0.97,
+tests/test_exact_cases_cpu.py); the f32 outputs use under a tenth of the K u term.  The same ops on integer operands,
+with zero tolerance: tests/test_ops_exact_gpu.py."""
 import ctypes as C
 import os
 
@@ -11,6 +24,8 @@ import torch.nn.functional as F
 
 import hlmc_amd
 from hlmc_amd import _lib as L
+from tests import exact_cases as X
+from tests.exact_cases import BB, BENCH_CONV, BENCH_SUBPIXEL, BENCH_WGRAD, HALO, HALO_EDGE
 
 pytestmark = pytest.mark.gpu
 DT = {"fp32": (L.HLMC_F32, torch.float32, 1e-5), "bf16": (L.HLMC_BF16, torch.bfloat16, 1e-2)}
@@ -32,12 +47,29 @@ def ws(cuda):
     return torch.empty(WS_BYTES, dtype=torch.uint8, device=cuda)
 
 
+def _conv_refs(kind, x, w, b):
+    """float64 reference of conv_s2 (kind 0, w [Co][Ci][3][3]) / subpixel (1, w [Ci][Co][3][3]) on an NHWC x, and
+    the same op on |operands| (assert_elementwise's absref); b may be None."""
+    def op(x_, w_, b_):
+        x_ = x_.permute(0, 3, 1, 2)
+        if kind == 0:
+            return F.conv2d(x_, w_, b_, stride=2, padding=1).permute(0, 2, 3, 1)
+        return F.conv_transpose2d(x_, w_, b_, stride=2, padding=1, output_padding=1).permute(0, 2, 3, 1)
+    x, w, b = x.double(), w.double(), None if b is None else b.double()
+    return op(x, w, b), op(x.abs(), w.abs(), None if b is None else b.abs())
+
+
+def _wgrad_refs(xh, lo, M, C):
+    """float64 conv2d_weight reference (high-res NHWC xh [.., C], low-res NHWC lo [.., M]) and its absref."""
+    def op(x_, l_):
+        return torch.nn.grad.conv2d_weight(x_.permute(0, 3, 1, 2), (M, C, 3, 3), l_.permute(0, 3, 1, 2), stride=2,
+                                           padding=1)
+    xh, lo = xh.double(), lo.double()
+    return op(xh, lo), op(xh.abs(), lo.abs())
+
+
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("B,Hi,Wi,Ci,Co", [(2, 16, 16, 32, 64), (2, 8, 8, 64, 128), (3, 4, 4, 128, 256),
-                                          (2, 4, 4, 256, 512), (2, 2, 2, 512, 512), (1, 8, 32, 32, 32),
-                                          (5, 4, 8, 64, 64), (3, 16, 64, 32, 64), (2, 64, 64, 32, 64),
-                                          (2, 32, 32, 64, 128), (3, 8, 32, 64, 128), (2, 16, 16, 128, 256),
-                                          (3, 32, 16, 128, 256)])
+@pytest.mark.parametrize("B,Hi,Wi,Ci,Co", X.CONV_S2)
 def test_conv_s2(cuda, ws, dt, B, Hi, Wi, Ci, Co):
     """(bf16 also covers the shapes of the LDS halo-tile kernels: Ci 32 -> Co 64 at Wi 64 and Ci 64 -> Co 128 at Wi 32;
     fp32 runs the gather GEMM at every shape)"""
@@ -46,7 +78,7 @@ def test_conv_s2(cuda, ws, dt, B, Hi, Wi, Ci, Co):
     x = torch.randn(B, Hi, Wi, Ci, generator=g)
     w = torch.randn(Co, Ci, 3, 3, generator=g) / (3 * Ci ** 0.5)
     b = torch.randn(Co, generator=g)
-    ref = F.conv2d(q(x, tdt).permute(0, 3, 1, 2), q(w, tdt), b.double(), stride=2, padding=1).permute(0, 2, 3, 1)
+    ref, absref = _conv_refs(0, q(x, tdt), q(w, tdt), b.double())
     xd = x.to(cuda, tdt).contiguous()
     wp = w.permute(0, 2, 3, 1).contiguous().to(cuda, tdt)
     y = torch.empty(B, Hi // 2, Wi // 2, Co, dtype=tdt, device=cuda)
@@ -54,13 +86,11 @@ def test_conv_s2(cuda, ws, dt, B, Hi, Wi, Ci, Co):
     L.check(L.lib().hlmc_op_conv_s2(L.stream(), code, xd.data_ptr(), B, Hi, Wi, Ci, wp.data_ptr(), bd.data_ptr(), Co,
                                     y.data_ptr(), ws.data_ptr(), WS_BYTES))
     assert rel(y, ref) < tol
+    X.assert_elementwise(y, ref, absref, 9 * Ci, tdt, f"conv_s2 {dt} {(B, Hi, Wi, Ci, Co)}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("B,Hi,Wi,Ci,Co", [(2, 2, 2, 512, 512), (2, 4, 4, 512, 256), (2, 8, 8, 256, 128),
-                                          (3, 16, 16, 128, 64), (2, 32, 32, 64, 32), (1, 2, 16, 512, 512),
-                                          (2, 4, 4, 32, 64), (3, 8, 32, 64, 32), (2, 16, 16, 128, 64),
-                                          (3, 8, 16, 128, 64), (2, 16, 8, 256, 128)])
+@pytest.mark.parametrize("B,Hi,Wi,Ci,Co", X.SUBPIXEL)
 def test_subpixel_convT(cuda, ws, dt, B, Hi, Wi, Ci, Co):
     """(the Ci 64 -> Co 32, 32-wide and Ci 128 -> Co 64, 16-wide shapes run the LDS halo-tile kernels in bf16; fp32
     runs the gather GEMM)"""
@@ -69,8 +99,7 @@ def test_subpixel_convT(cuda, ws, dt, B, Hi, Wi, Ci, Co):
     x = torch.randn(B, Hi, Wi, Ci, generator=g)
     w = torch.randn(Ci, Co, 3, 3, generator=g) / (3 * Ci ** 0.5)   # ConvTranspose2d weight layout
     b = torch.randn(Co, generator=g)
-    ref = F.conv_transpose2d(q(x, tdt).permute(0, 3, 1, 2), q(w, tdt), b.double(), stride=2, padding=1,
-                             output_padding=1).permute(0, 2, 3, 1)
+    ref, absref = _conv_refs(1, q(x, tdt), q(w, tdt), b.double())
     xd = x.to(cuda, tdt).contiguous()
     wp = w.permute(1, 2, 3, 0).contiguous().to(cuda, tdt)           # [Co][kh][kw][Ci]
     y = torch.empty(B, 2 * Hi, 2 * Wi, Co, dtype=tdt, device=cuda)
@@ -78,17 +107,11 @@ def test_subpixel_convT(cuda, ws, dt, B, Hi, Wi, Ci, Co):
     L.check(L.lib().hlmc_op_subpixel(L.stream(), code, xd.data_ptr(), B, Hi, Wi, Ci, wp.data_ptr(), bd.data_ptr(), Co,
                                      y.data_ptr(), ws.data_ptr(), WS_BYTES))
     assert rel(y, ref) < tol
+    X.assert_elementwise(y, ref, absref, 9 * Ci, tdt, f"subpixel {dt} {(B, Hi, Wi, Ci, Co)}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("B,Hl,Wl,M,C", [(2, 8, 8, 64, 32), (2, 4, 4, 128, 64), (2, 2, 2, 512, 256),
-                                        (3, 1, 1, 512, 512), (2, 16, 16, 32, 64), (4, 2, 8, 256, 128),
-                                        (3, 8, 32, 64, 32), (1, 32, 32, 64, 32),
-                                        # the conv-layout split-K reduces (plan_tn; G: the grouped reduce's groups)
-                                        (8, 8, 8, 128, 128),    # bf16 S 2 / fp32 S 4: 16-byte conv reduce (C % 128)
-                                        (16, 8, 8, 128, 128),   # bf16 S 4: 16-byte conv reduce; fp32 S 8: grouped, G 4
-                                        (12, 8, 8, 64, 32),     # 96-wide; bf16 S 3: 4-byte conv reduce, tail; fp32 S 6: G 2
-                                        (2, 4, 4, 16, 16)])     # S 1, C % 32 != 0: the grouped reduce's scattered store
+@pytest.mark.parametrize("B,Hl,Wl,M,C", X.WGRAD_S2)
 def test_wgrad_s2_conv(cuda, ws, dt, B, Hl, Wl, M, C):
     """Conv2d weight gradient: L = dY (low-res, M=Co), Xh = X (high-res, C=Ci), through the weight-gradient TN GEMM
     (the B = 256 bench shapes are test_wgrad_s2_bench_shapes_bf16)."""
@@ -96,42 +119,39 @@ def test_wgrad_s2_conv(cuda, ws, dt, B, Hl, Wl, M, C):
     g = torch.Generator().manual_seed(M + C + B)
     dy = torch.randn(B, Hl, Wl, M, generator=g)
     x = torch.randn(B, 2 * Hl, 2 * Wl, C, generator=g)
-    ref = torch.nn.grad.conv2d_weight(q(x, tdt).permute(0, 3, 1, 2), (M, C, 3, 3), q(dy, tdt).permute(0, 3, 1, 2),
-                                      stride=2, padding=1)
+    ref, absref = _wgrad_refs(q(x, tdt), q(dy, tdt), M, C)
     dW = torch.empty(M, C, 3, 3, device=cuda)
     dyd, xd = dy.to(cuda, tdt).contiguous(), x.to(cuda, tdt).contiguous()
     L.check(L.lib().hlmc_op_wgrad_s2(L.stream(), code, dyd.data_ptr(), B, Hl, Wl, M, xd.data_ptr(), C, dW.data_ptr(),
                                      ws.data_ptr(), WS_BYTES))
     assert rel(dW, ref) < (1e-5 if dt == "fp32" else 5e-3)
+    X.assert_elementwise(dW, ref, absref, B * Hl * Wl, torch.float32, f"wgrad_s2 {dt} {(B, Hl, Wl, M, C)}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 def test_wgrad_s2_convT(cuda, ws, dt):
     """ConvTranspose2d weight gradient: L = X (low-res input, M=Ci), Xh = dY (high-res, C=Co)."""
     code, tdt, tol = DT[dt]
-    B, Hl, Wl, Ci, Co = 2, 4, 4, 128, 64
+    B, Hl, Wl, Ci, Co = X.WGRAD_S2_CONVT
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, Hl, Wl, Ci, generator=g)
     dy = torch.randn(B, 2 * Hl, 2 * Wl, Co, generator=g)
     w = torch.zeros(Ci, Co, 3, 3, dtype=torch.float64, requires_grad=True)
     out = F.conv_transpose2d(q(x, tdt).permute(0, 3, 1, 2), w, stride=2, padding=1, output_padding=1)
     out.backward(q(dy, tdt).permute(0, 3, 1, 2))
+    wa = torch.zeros(Ci, Co, 3, 3, dtype=torch.float64, requires_grad=True)   # the same on |operands|
+    F.conv_transpose2d(q(x, tdt).abs().permute(0, 3, 1, 2), wa, stride=2, padding=1, output_padding=1).backward(
+        q(dy, tdt).abs().permute(0, 3, 1, 2))
     dW = torch.empty(Ci, Co, 3, 3, device=cuda)
     xd, dyd = x.to(cuda, tdt).contiguous(), dy.to(cuda, tdt).contiguous()
     L.check(L.lib().hlmc_op_wgrad_s2(L.stream(), code, xd.data_ptr(), B, Hl, Wl, Ci, dyd.data_ptr(), Co,
                                      dW.data_ptr(), ws.data_ptr(), WS_BYTES))
     assert rel(dW, w.grad) < (1e-5 if dt == "fp32" else 5e-3)
+    X.assert_elementwise(dW, w.grad, wa.grad, B * Hl * Wl, torch.float32, f"wgrad_s2 convT {dt}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("M,K,N,ldx,act,acc", [(4, 768, 256, 768, 0, 0), (256, 2048, 1024, 2048, 0, 0),
-                                              (5, 370, 128, 376, 1, 0), (256, 2314, 64, 2320, 0, 1),
-                                              (33, 128, 1152, 136, 1, 0), (256, 74, 2304, 80, 0, 0),
-                                              (2, 1024, 16384, 1152, 0, 0), (2, 1024, 16384, 1152, 0, 1),
-                                              # N % 4 != 0: the scalar NT split-K reduce (plan_nt, one 64 x 64 tile)
-                                              (3, 384, 42, 384, 0, 0),   # bf16 S 3: tail only; fp32 S 6: 4 + 2
-                                              (3, 512, 42, 512, 0, 0),   # bf16 S 4: one group of 4, no tail; fp32 S 8
-                                              (3, 896, 42, 896, 0, 1)])  # bf16 S 7: 4 + 3; fp32 S 14: 4 + 4 + 4 + 2
+@pytest.mark.parametrize("M,K,N,ldx,act,acc", X.LINEAR)
 def test_linear(cuda, ws, dt, M, K, N, ldx, act, acc):
     code, tdt, tol = DT[dt]
     g = torch.Generator().manual_seed(M + K + N)
@@ -140,10 +160,12 @@ def test_linear(cuda, ws, dt, M, K, N, ldx, act, acc):
     b = torch.randn(N, generator=g)
     y0 = torch.randn(M, N, generator=g)
     ref = q(x[:, :K], tdt) @ q(w, tdt).T + b.double()
+    absref = q(x[:, :K], tdt).abs() @ q(w, tdt).abs().T + b.double().abs()
     if act:
         ref = ref.clamp_min(0)
     if acc:
         ref = ref + q(y0, tdt)
+        absref = absref + q(y0, tdt).abs()
     ldw = ((K + 7) // 8) * 8
     wpad = torch.zeros(N, ldw)
     wpad[:, :K] = w
@@ -152,10 +174,11 @@ def test_linear(cuda, ws, dt, M, K, N, ldx, act, acc):
     L.check(L.lib().hlmc_op_linear(L.stream(), code, xd.data_ptr(), ldx, M, K, wd.data_ptr(), ldw, bd.data_ptr(), N,
                                    y.data_ptr(), N, act, acc, 0, ws.data_ptr(), WS_BYTES, None))
     assert rel(y, ref) < tol
+    X.assert_elementwise(y, ref, absref, K, tdt, f"linear {dt} {(M, K, N, ldx, act, acc)}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("M,K,N,acc", [(256, 2048, 1024, 0), (256, 512, 512, 1), (4, 16384, 1024, 0), (3, 64, 40, 1)])
+@pytest.mark.parametrize("M,K,N,acc", X.LINEAR_RELU_MASK)
 def test_linear_relu_mask(cuda, ws, dt, M, K, N, acc):
     """Dense data gradient with the ReLU backward of the layer below in the epilogue (engine.cpp lin_bwd)."""
     code, tdt, tol = DT[dt]
@@ -165,9 +188,12 @@ def test_linear_relu_mask(cuda, ws, dt, M, K, N, acc):
     y0 = torch.randn(M, N, generator=g)
     act = torch.randn(M, N, generator=g).clamp_min(0)  # post-ReLU activation: ~half the entries exactly 0
     ref = q(x, tdt) @ q(w, tdt).T
+    absref = q(x, tdt).abs() @ q(w, tdt).abs().T
     if acc:
         ref = ref + q(y0, tdt)
+        absref = absref + q(y0, tdt).abs()
     ref = torch.where(q(act, tdt) > 0, ref, torch.zeros_like(ref))
+    absref = torch.where(q(act, tdt) > 0, absref, torch.zeros_like(absref))
     y = y0.to(cuda, tdt).contiguous()
     xd, wd, ad = x.to(cuda, tdt).contiguous(), w.to(cuda, tdt).contiguous(), act.to(cuda, tdt).contiguous()
     L.check(L.lib().hlmc_op_linear(L.stream(), code, xd.data_ptr(), K, M, K, wd.data_ptr(), K, None, N,
@@ -175,17 +201,11 @@ def test_linear_relu_mask(cuda, ws, dt, M, K, N, acc):
     torch.cuda.synchronize()
     assert rel(y, ref) < tol
     assert bool((y.float().cpu()[act.to(tdt) <= 0] == 0).all())
+    X.assert_elementwise(y, ref, absref, K, tdt, f"linear relu mask {dt} {(M, K, N, acc)}")
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
-@pytest.mark.parametrize("Mb,N,K", [(4, 256, 768), (256, 1024, 2048), (32, 128, 370), (256, 64, 2314),
-                                    (7, 2048, 1024),
-                                    # the grouped TN reduce at both widths (8 columns: float4; 9 with the bias: scalar),
-                                    # one 32 x 128 tile (plan_tn): S (G groups) fp32 / bf16
-                                    (300, 8, 8),     # 2, ragged (1) / 1 (1)
-                                    (512, 8, 8),     # 4 (2) / 2 (1)
-                                    (1024, 8, 8),    # 8 (4) / 4 (2)
-                                    (4096, 8, 8)])   # 32 (8) / 16 (4)
+@pytest.mark.parametrize("Mb,N,K", X.LINEAR_WGRAD)
 def test_linear_wgrad(cuda, ws, dt, Mb, N, K):
     code, tdt, tol = DT[dt]
     g = torch.Generator().manual_seed(Mb + N + K)
@@ -193,6 +213,7 @@ def test_linear_wgrad(cuda, ws, dt, Mb, N, K):
     dy = torch.randn(Mb, ldd, generator=g)
     x = torch.randn(Mb, ldx, generator=g)
     ref = q(dy[:, :N], tdt).T @ q(x[:, :K], tdt)
+    absref = q(dy[:, :N], tdt).abs().T @ q(x[:, :K], tdt).abs()
     ref_b = q(dy[:, :N], tdt).sum(0)
     dyd, xd = dy.to(cuda, tdt).contiguous(), x.to(cuda, tdt).contiguous()
     for with_bias in (False, True):  # the bias gradient through the GEMM's ones column, and without it
@@ -203,6 +224,7 @@ def test_linear_wgrad(cuda, ws, dt, Mb, N, K):
                                              WS_BYTES))
         torch.cuda.synchronize()
         assert rel(dW, ref) < (1e-5 if dt == "fp32" else 5e-3)
+        X.assert_elementwise(dW, ref, absref, Mb, torch.float32, f"linear_wgrad {dt} {(Mb, N, K)} db={with_bias}")
         if with_bias:
             assert rel(db, ref_b) < 1e-5  # dy x 1 is exact in either dtype; f32 accumulation
         else:
@@ -211,7 +233,7 @@ def test_linear_wgrad(cuda, ws, dt, Mb, N, K):
 
 # the bench's 128 x 128 clip and a 128 x 1024 mel row band besides the small case; (16, 128, 128) gives the row-staged
 # weight gradient (64-wide layers) two rows per block
-@pytest.mark.parametrize("shape", [(3, 16, 32), (2, 128, 128), (2, 32, 64), (1, 16, 1024), (16, 128, 128)])
+@pytest.mark.parametrize("shape", X.EDGE_CONVS)
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 def test_edge_convs(cuda, ws, dt, shape):
     code, tdt, tol = DT[dt]
@@ -221,35 +243,36 @@ def test_edge_convs(cuda, ws, dt, shape):
     w1 = torch.randn(32, 1, 3, 3, generator=g) / 3
     b1 = torch.randn(32, generator=g)
     # conv1 forward
-    ref = F.conv2d(img.double()[:, None], w1.double(), b1.double(), stride=2, padding=1).permute(0, 2, 3, 1)
+    ref, absref = _conv_refs(0, img[..., None], w1, b1)
     y = torch.empty(B, H // 2, W // 2, 32, dtype=tdt, device=cuda)
     imgd, w1d, b1d = img.to(cuda), w1.to(cuda), b1.to(cuda)
     L.check(L.lib().hlmc_op_conv_c1_s2(L.stream(), code, imgd.data_ptr(), B, H, W, w1d.data_ptr(), b1d.data_ptr(), 32,
                                        y.data_ptr()))
     assert rel(y, ref) < (1e-6 if dt == "fp32" else 1e-2)
+    X.assert_elementwise(y, ref, absref, 9, tdt, f"conv_c1_s2 {dt} {shape}")
     # last convT (32 -> 1)
     a = torch.randn(B, H // 2, W // 2, 32, generator=g)
     wT = torch.randn(32, 1, 3, 3, generator=g) / 10
     bT = torch.randn(1, generator=g)
-    refT = F.conv_transpose2d(q(a, tdt).permute(0, 3, 1, 2), wT.double(), bT.double(), stride=2, padding=1,
-                              output_padding=1)[:, 0]
+    refT, absrefT = (t[..., 0] for t in _conv_refs(1, q(a, tdt), wT, bT))
     out = torch.empty(B, H, W, device=cuda)
     ad, wTd, bTd = a.to(cuda, tdt).contiguous(), wT.to(cuda), bT.to(cuda)
     L.check(L.lib().hlmc_op_convT_c1(L.stream(), code, ad.data_ptr(), B, H // 2, W // 2, 32, wTd.data_ptr(),
                                      bTd.data_ptr(), out.data_ptr()))
     assert rel(out, refT) < 1e-6
+    X.assert_elementwise(out, refT, absrefT, 9 * 32, torch.float32, f"convT_c1 {dt} {shape}")
     # weight gradients of both (one-channel high-res side)
     dy = torch.randn(B, H // 2, W // 2, 32, generator=g)
-    refw = torch.nn.grad.conv2d_weight(img.double()[:, None], (32, 1, 3, 3), q(dy, tdt).permute(0, 3, 1, 2),
-                                       stride=2, padding=1)
+    refw, absrefw = _wgrad_refs(img[..., None], q(dy, tdt), 32, 1)
     dW = torch.empty(32, 1, 3, 3, device=cuda)
     dyd = dy.to(cuda, tdt).contiguous()
     L.check(L.lib().hlmc_op_wgrad_c1(L.stream(), code, dyd.data_ptr(), B, H // 2, W // 2, 32, imgd.data_ptr(),
                                      dW.data_ptr(), ws.data_ptr(), WS_BYTES))
     assert rel(dW, refw) < 1e-5
+    X.assert_elementwise(dW, refw, absrefw, B * (H // 2) * (W // 2), torch.float32, f"wgrad_c1 {dt} {shape}")
 
 
-@pytest.mark.parametrize("shape", [(1, 7, 64), (3, 11, 64), (1, 5, 64), (2, 9, 24)])
+@pytest.mark.parametrize("shape", X.WGRAD_C1_ODD)
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
 def test_wgrad_c1_odd_heights(cuda, ws, dt, shape):
     """hlmc_op_wgrad_c1 at odd low-res heights and B = 1 (Xh is [B][2 Hl][2 Wl] f32, include/hlmc.h): the row-streamed
@@ -260,14 +283,14 @@ def test_wgrad_c1_odd_heights(cuda, ws, dt, shape):
     g = torch.Generator().manual_seed(Hl * 31 + B)
     img = torch.randn(B, 2 * Hl, 2 * Wl, generator=g)
     dy = torch.randn(B, Hl, Wl, 32, generator=g)
-    refw = torch.nn.grad.conv2d_weight(img.double()[:, None], (32, 1, 3, 3), q(dy, tdt).permute(0, 3, 1, 2),
-                                       stride=2, padding=1)
+    refw, absrefw = _wgrad_refs(img[..., None], q(dy, tdt), 32, 1)
     dW = torch.empty(32, 1, 3, 3, device=cuda)
     imgd, dyd = img.to(cuda), dy.to(cuda, tdt).contiguous()
     L.check(L.lib().hlmc_op_wgrad_c1(L.stream(), code, dyd.data_ptr(), B, Hl, Wl, 32, imgd.data_ptr(), dW.data_ptr(),
                                      ws.data_ptr(), WS_BYTES))
     torch.cuda.synchronize()
     assert rel(dW, refw) < 1e-5
+    X.assert_elementwise(dW, refw, absrefw, B * Hl * Wl, torch.float32, f"wgrad_c1 {dt} {shape}")
 
 
 @pytest.mark.parametrize("nt", [0, 4 * 384])
@@ -312,14 +335,11 @@ def test_loss_sums_backward_fused_equals_separate(cuda, nt):
 # layers on the <= 512-block LDS-DMA ring, the rest on the register-staged GEMM; the weight gradients' split-K
 # slabs (up to 342 splits) and their grouped reduction.  Encoder forward conv shapes = the decoder's data-gradient
 # convs, decoder sub-pixel shapes = the encoder's data gradients, and the ten weight gradients reduce to five
-# (M, C, Hl, Wl) shapes.  Reference: CPU float32 on the same bf16-rounded operands (its own error ~1e-6).
+# (M, C, Hl, Wl) shapes.  Reference: CPU float64 on the same bf16-rounded operands.
 #   NT (bf16 output): rel L2 <= 3e-3 (output rounding alone is ~1.1e-3; a dropped K-split of S <= 16 costs >= 6%)
 #   weight gradients (fp32 output, fp32 accumulation of bf16 products): rel L2 <= 1e-4 (one dropped slab of the
 #   deepest 342-way split costs ~3e-3)
-BENCH_CONV = [(64, 64, 32, 64), (32, 32, 64, 128), (16, 16, 128, 256), (8, 8, 256, 512), (4, 4, 512, 512)]
-BENCH_SUBPIXEL = [(2, 2, 512, 512), (4, 4, 512, 256), (8, 8, 256, 128), (16, 16, 128, 64), (32, 32, 64, 32)]
-BENCH_WGRAD = [(32, 32, 64, 32), (16, 16, 128, 64), (8, 8, 256, 128), (4, 4, 512, 256), (2, 2, 512, 512)]
-BB = 256
+# (BENCH_CONV, BENCH_SUBPIXEL, BENCH_WGRAD and BB = 256: tests/exact_cases.py)
 
 
 @pytest.mark.parametrize("Hi,Wi,Ci,Co", BENCH_CONV)
@@ -328,7 +348,7 @@ def test_conv_s2_bench_shapes_bf16(cuda, ws, Hi, Wi, Ci, Co):
     x = torch.randn(BB, Hi, Wi, Ci, generator=g).to(torch.bfloat16)
     w = (torch.randn(Co, Ci, 3, 3, generator=g) / (3 * Ci ** 0.5)).to(torch.bfloat16)
     b = torch.randn(Co, generator=g)
-    ref = F.conv2d(x.float().permute(0, 3, 1, 2), w.float(), b, stride=2, padding=1).permute(0, 2, 3, 1)
+    ref, absref = _conv_refs(0, x, w, b)
     xd = x.to(cuda).contiguous()
     wp = w.permute(0, 2, 3, 1).contiguous().to(cuda)
     y = torch.empty(BB, Hi // 2, Wi // 2, Co, dtype=torch.bfloat16, device=cuda)
@@ -338,6 +358,7 @@ def test_conv_s2_bench_shapes_bf16(cuda, ws, Hi, Wi, Ci, Co):
     e = rel(y, ref)
     print(f"conv_s2 B={BB} {Hi}x{Wi} {Ci}->{Co}: rel L2 {e:.2e}")
     assert e < 3e-3
+    X.assert_elementwise(y, ref, absref, 9 * Ci, torch.bfloat16, f"conv_s2 bf16 B={BB} {(Hi, Wi, Ci, Co)}")
 
 
 @pytest.mark.parametrize("Hi,Wi,Ci,Co", BENCH_SUBPIXEL)
@@ -346,8 +367,7 @@ def test_subpixel_bench_shapes_bf16(cuda, ws, Hi, Wi, Ci, Co):
     x = torch.randn(BB, Hi, Wi, Ci, generator=g).to(torch.bfloat16)
     w = (torch.randn(Ci, Co, 3, 3, generator=g) / (3 * Ci ** 0.5)).to(torch.bfloat16)
     b = torch.randn(Co, generator=g)
-    ref = F.conv_transpose2d(x.float().permute(0, 3, 1, 2), w.float(), b, stride=2, padding=1,
-                             output_padding=1).permute(0, 2, 3, 1)
+    ref, absref = _conv_refs(1, x, w, b)
     xd = x.to(cuda).contiguous()
     wp = w.permute(1, 2, 3, 0).contiguous().to(cuda)
     y = torch.empty(BB, 2 * Hi, 2 * Wi, Co, dtype=torch.bfloat16, device=cuda)
@@ -357,6 +377,7 @@ def test_subpixel_bench_shapes_bf16(cuda, ws, Hi, Wi, Ci, Co):
     e = rel(y, ref)
     print(f"subpixel B={BB} {Hi}x{Wi} {Ci}->{Co}: rel L2 {e:.2e}")
     assert e < 3e-3
+    X.assert_elementwise(y, ref, absref, 9 * Ci, torch.bfloat16, f"subpixel bf16 B={BB} {(Hi, Wi, Ci, Co)}")
 
 
 @pytest.mark.parametrize("Hl,Wl,M,C", BENCH_WGRAD)
@@ -364,8 +385,7 @@ def test_wgrad_s2_bench_shapes_bf16(cuda, ws, Hl, Wl, M, C):
     g = torch.Generator().manual_seed(Hl * 13 + M + C)
     dy = torch.randn(BB, Hl, Wl, M, generator=g).to(torch.bfloat16)
     x = torch.randn(BB, 2 * Hl, 2 * Wl, C, generator=g).to(torch.bfloat16)
-    ref = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (M, C, 3, 3), dy.double().permute(0, 3, 1, 2),
-                                      stride=2, padding=1)
+    ref, absref = _wgrad_refs(x, dy, M, C)
     dW = torch.empty(M, C, 3, 3, device=cuda)
     dyd, xd = dy.to(cuda).contiguous(), x.to(cuda).contiguous()   # held: a freed temporary's block gets reused
     L.check(L.lib().hlmc_op_wgrad_s2(L.stream(), L.HLMC_BF16, dyd.data_ptr(), BB, Hl, Wl, M, xd.data_ptr(), C,
@@ -373,6 +393,7 @@ def test_wgrad_s2_bench_shapes_bf16(cuda, ws, Hl, Wl, M, C):
     e = rel(dW, ref)
     print(f"wgrad_s2 B={BB} {Hl}x{Wl} M={M} C={C}: rel L2 {e:.2e}")
     assert e < 1e-4
+    X.assert_elementwise(dW, ref, absref, BB * Hl * Wl, torch.float32, f"wgrad_s2 bf16 B={BB} {(Hl, Wl, M, C)}")
 
 
 def test_device_randn_matches_philox_restatement(cuda):
@@ -409,22 +430,13 @@ def test_device_randn_matches_philox_restatement(cuda):
 # engine launches it — epilogue statistics accumulated per lane over all of a persistent block's tiles (8 tiles per
 # block at these shapes) and, with bn_in, the layer below's BatchNorm + LeakyReLU applied while the input is staged
 # (BnInput; src/Convolutional_VAE.py:80-100 encoder, :124-139 decoder).  Checked:
-#   * output vs CPU float32 conv of the bf16 operands (the kernel's own activation a_out as input): rel L2 <= 3e-3;
+#   * output vs CPU float64 conv of the bf16 operands (the kernel's own activation a_out as input): rel L2 <= 3e-3
+#     and every element within assert_elementwise's bound;
 #   * out_sums vs the float64 sums of the kernel's own bf16 output: rel <= 1e-9 (exact accumulator, f64 order only);
 #   * bn_in: batch mean / invstd vs float64 statistics of the input <= 1e-6 rel; running statistics as torch's
 #     BatchNorm2d(momentum 0.1) updates them; num_batches_tracked 1; a_out = bf16(LeakyReLU((x - mean) * invstd *
 #     gamma + beta)) within one bf16 ulp, <= 0.1 % of elements off by that ulp (fp32 contraction order).
-HALO = [(0, 64, 64, 32, 64), (0, 32, 32, 64, 128), (1, 32, 32, 64, 32), (1, 16, 16, 128, 64)]
-
-
-# Edge shapes of the same four layers (B, Hi): the persistent tile walk where it is not a whole number of equal passes.
-#   minimal: B = 1 at the smallest legal height: fewer tiles than the grid cap (grid = tiles x channel splits), the
-#     prefetch clamped on the block's only tile; the three one-tile shapes' tile is both first and last of its image
-#     (zero row above / below, a_out ownership);
-#   uneven: two tiles per image and two more tiles than a channel split has blocks (514 / 512, 130 / 128): two blocks
-#     walk two tiles, the rest one.
-HALO_EDGE = [(0, 1, 8, 64, 32, 64), (0, 1, 8, 32, 64, 128), (1, 1, 4, 32, 64, 32), (1, 1, 8, 16, 128, 64),
-             (0, 257, 8, 64, 32, 64), (0, 65, 16, 32, 64, 128), (1, 257, 8, 32, 64, 32), (1, 65, 16, 16, 128, 64)]
+# (HALO, the four shapes at B = 256, and HALO_EDGE, their edge shapes: tests/exact_cases.py)
 
 
 def _halo_operands(g, kind, B, Hi, Wi, Ci, Co):
@@ -439,12 +451,8 @@ def _halo_operands(g, kind, B, Hi, Wi, Ci, Co):
 
 
 def _halo_reference(kind, inp, w, b):
-    x = inp.float().permute(0, 3, 1, 2)
-    if kind == 0:
-        ref = F.conv2d(x, w.float(), b, stride=2, padding=1)
-    else:
-        ref = F.conv_transpose2d(x, w.float(), b, stride=2, padding=1, output_padding=1)
-    return ref.permute(0, 2, 3, 1)
+    """float64 reference and absref (_conv_refs) of a halo-shape conv on the bf16 operands."""
+    return _conv_refs(kind, inp, w, b)
 
 
 @pytest.mark.parametrize("bn_in", [False, True], ids=["stats", "bn_in+stats"])
@@ -462,7 +470,8 @@ def test_halo_fwd_bn_stats_edge_shapes(cuda, kind, B, Hi, Wi, Ci, Co, bn_in):
 @pytest.mark.parametrize("kind,B,Hi,Wi,Ci,Co", HALO_EDGE)
 def test_halo_plain_edge_shapes(cuda, ws, kind, B, Hi, Wi, Ci, Co):
     """The plain form of the halo kernels (no statistics: hlmc_op_conv_s2 / hlmc_op_subpixel, bf16) at the edge shapes
-    vs the CPU float32 conv of the bf16 operands: rel L2 < 3e-3 (test_conv_s2_bench_shapes_bf16's bound)."""
+    vs the CPU float64 conv of the bf16 operands: rel L2 < 3e-3 (test_conv_s2_bench_shapes_bf16's bound) and every
+    element within assert_elementwise's bound."""
     g = torch.Generator().manual_seed(kind * 100 + Hi + Ci + B)
     x, w, wp, oshape = _halo_operands(g, kind, B, Hi, Wi, Ci, Co)
     b = torch.randn(Co, generator=g) * 0.1
@@ -471,9 +480,11 @@ def test_halo_plain_edge_shapes(cuda, ws, kind, B, Hi, Wi, Ci, Co):
     op = L.lib().hlmc_op_conv_s2 if kind == 0 else L.lib().hlmc_op_subpixel
     L.check(op(L.stream(), L.HLMC_BF16, xd.data_ptr(), B, Hi, Wi, Ci, wd.data_ptr(), bd.data_ptr(), Co, y.data_ptr(),
                ws.data_ptr(), WS_BYTES))
-    e = rel(y, _halo_reference(kind, x, w, b))
+    ref, absref = _halo_reference(kind, x, w, b)
+    e = rel(y, ref)
     print(f"halo plain kind {kind} B={B} {Hi}x{Wi} {Ci}->{Co}: rel L2 {e:.2e}")
     assert e < 3e-3
+    X.assert_elementwise(y, ref, absref, 9 * Ci, torch.bfloat16, f"halo plain kind {kind} {(B, Hi, Wi, Ci, Co)}")
 
 
 def _halo_fwd_case(cuda, kind, B, Hi, Wi, Ci, Co, bn_in):
@@ -520,7 +531,8 @@ def _halo_fwd_case(cuda, kind, B, Hi, Wi, Ci, Co, bn_in):
         inp = got
     else:
         assert torch.equal(d["rm"].cpu(), rm0) and int(nbt.item()) == 0   # untouched without gamma
-    e = rel(y, _halo_reference(kind, inp, w, b))
+    ref, absref = _halo_reference(kind, inp, w, b)
+    e = rel(y, ref)
     yo = y.cpu().double().reshape(-1, Co)
     s_ref = torch.cat([yo.sum(0), (yo * yo).sum(0)])
     e_s = float(((sums.cpu() - s_ref).abs() / s_ref.abs().clamp_min(1e-300)).max())
@@ -529,6 +541,8 @@ def _halo_fwd_case(cuda, kind, B, Hi, Wi, Ci, Co, bn_in):
     e_s2 = float(((sums.cpu()[Co:] - s_ref[Co:]).abs() / s_ref[Co:]).max())
     print(f"halo kind {kind} B={B} {Hi}x{Wi} {Ci}->{Co} bn_in={bn_in}: rel L2 {e:.2e}, stats {e_s1:.1e} / {e_s2:.1e}")
     assert e < 3e-3 and e_s1 < 1e-9 and e_s2 < 1e-9
+    X.assert_elementwise(y, ref, absref, 9 * Ci, torch.bfloat16,
+                         f"halo_fwd kind {kind} {(B, Hi, Wi, Ci, Co)} bn_in={bn_in}")
 
 
 def test_halo_fwd_rejects_other_shapes(cuda):
