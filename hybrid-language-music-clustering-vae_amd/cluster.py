@@ -72,6 +72,19 @@ def _euclid_f32(a, b):
     return r
 
 
+def _pinned_like(t):
+    return torch.empty(t.shape, dtype=t.dtype).pin_memory()
+
+
+def _copy_back(dev, pairs):
+    """The one copy back of a k-means++ step / Lloyd iteration: asynchronous copies into preallocated pinned host
+    images ((pinned, device) pairs), one stream synchronisation, numpy views (valid until the image is reused)."""
+    for pin, src in pairs:
+        pin.copy_(src, non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    return [pin.numpy() for pin, _ in pairs]
+
+
 class KMeans:
     def __init__(self, n_clusters=8, *, init="k-means++", n_init="auto", max_iter=300, tol=1e-4, verbose=0,
                  random_state=None, copy_x=True, algorithm="lloyd", device=None, process_group=None):
@@ -146,13 +159,10 @@ class KMeans:
         cand = torch.empty(R * T, dtype=torch.int64, device=dev)
         amb = torch.empty(R * T, dtype=torch.int32, device=dev)
         # two pinned host images of the distances (this step's and the previous step's closest rows)
-        pins = [torch.empty(R, T, n, dtype=torch.float32).pin_memory() for _ in range(2)] if dev.type == "cuda" else None
-        if pins is not None:
-            cpin = torch.empty(R * T, dtype=torch.int64).pin_memory()
-            apin = torch.empty(R * T, dtype=torch.int32).pin_memory()
+        pins = [_pinned_like(b) for b in bufs]
+        cpin, apin = _pinned_like(cand), _pinned_like(amb)
         for c in range(1, k):
             out = bufs[c % 2]
-            pin = pins[c % 2] if pins is not None else None
             rv = np.stack([seeds[r][1][c - 1] * pots[r] for r in range(R)]).astype(np.float64)   # rand_vals
             prevT = prev.shape[1]
             bh = best.ctypes.data_as(C.POINTER(C.c_int32))
@@ -161,16 +171,9 @@ class KMeans:
                                           cand.data_ptr(), amb.data_ptr()), "hlmc_km_pp_search")
             L.check(lib.hlmc_km_pp_dist(L.stream(), Xc.data_ptr(), n, d, R, T, cand.data_ptr(), prev.data_ptr(),
                                         prevT, bh, out.data_ptr()), "hlmc_km_pp_dist")
-            if pin is not None:   # one synchronisation per step: the distances, candidates and flags
-                pin.copy_(out, non_blocking=True)
-                cpin.copy_(cand, non_blocking=True)
-                apin.copy_(amb, non_blocking=True)
-                torch.cuda.current_stream(dev).synchronize()
-                cand_h, amb_h = cpin.numpy().reshape(R, T).copy(), apin.numpy().reshape(R, T)
-                out_h = pin.numpy()
-            else:
-                cand_h, amb_h = cand.cpu().numpy().reshape(R, T), amb.cpu().numpy().reshape(R, T)
-                out_h = out.cpu().numpy()
+            # one synchronisation per step: the distances, candidates and flags
+            out_h, cand_h, amb_h = _copy_back(dev, [(pins[c % 2], out), (cpin, cand), (apin, amb)])
+            cand_h, amb_h = cand_h.reshape(R, T).copy(), amb_h.reshape(R, T)
             for r in range(R):
                 closest = prev_h[r, best[r]][None, :]
                 dist = out_h[r]
@@ -188,7 +191,7 @@ class KMeans:
                 pots[r] = cpot[b]
                 best[r] = b
                 idx[r, c] = cand_h[r, b]
-            prev, prev_h = out, (out_h if pin is not None else out_h.copy())
+            prev, prev_h = out, out_h
         cent = Xc[torch.as_tensor(idx.reshape(-1), device=dev)].reshape(R, k, d).contiguous()
         return cent, idx
 
@@ -213,9 +216,7 @@ class KMeans:
         ws_bytes = int(lib.hlmc_km_sums_workspace(n, k)) * R
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         old_c = cbuf[0].cpu().numpy()
-        pinned = dev.type == "cuda"
-        pack_p = torch.empty(pack.shape, dtype=torch.float32).pin_memory() if pinned else None
-        cen_p = torch.empty(centers.shape, dtype=torch.float32).pin_memory() if pinned else None
+        pack_p, cen_p = _pinned_like(pack), _pinned_like(centers)
         final_c = old_c.copy()
         final_lab = torch.empty(R, n, dtype=torch.int32, device=dev)
         n_iter = np.zeros(R, dtype=np.int64)
@@ -234,13 +235,8 @@ class KMeans:
                                            sums.data_ptr(), wts.data_ptr(), ws.data_ptr(), ws_bytes))
             L.check(lib.hlmc_km_update_batch(L.stream(), k, d, R, active, sums.data_ptr(), wts.data_ptr(),
                                              cur.data_ptr(), nxt.data_ptr(), info.data_ptr()))
-            if pinned:   # one synchronisation per iteration: counts, shifts and the new centres
-                pack_p.copy_(pack, non_blocking=True)
-                cen_p.copy_(nxt, non_blocking=True)
-                torch.cuda.current_stream(dev).synchronize()
-                pack_h, nxt_h = pack_p.numpy(), cen_p.numpy()
-            else:
-                pack_h, nxt_h = pack.cpu().numpy(), nxt.cpu().numpy()
+            # one synchronisation per iteration: counts, shifts and the new centres
+            pack_h, nxt_h = _copy_back(dev, [(pack_p, pack), (cen_p, nxt)])
             info_h = pack_h[:R * (k + 1)].reshape(R, k + 1)
             chg = pack_h[R * (k + 1):].view(np.int32)
             for r in range(R):

@@ -7,6 +7,7 @@
 
 #include "engine.hpp"
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 
@@ -565,11 +566,18 @@ int hlmc_op_wgrad_c1(void* stream, int dtype, const void* Lo, int B, int Hl, int
                        ops::wgrad_c1<bf16>(S(stream), (const bf16*)Lo, B, Hl, Wl, M, Xh, dW, w));
 }
 
-int64_t hlmc_op_bn_bwd_workspace(int C) {
-    if (C <= 0) return 0;
-    return (int64_t)(((ops::bn_acc_bytes(C) + 255) & ~(size_t)255) + ((ops::bias_acc_bytes(C) + 255) & ~(size_t)255) +
-                     2 * (size_t)C * sizeof(float));
+// hlmc_op_bn_bwd workspace: moments accumulator mom | bias accumulator bacc (both zeroed: [0, sums)) | sums [2 C] f32
+struct BnBwdLayout { size_t mom, bacc, sums, total; };
+static BnBwdLayout bn_bwd_layout(int C) {
+    BnBwdLayout l;
+    Carver c;
+    l.mom = c.take(ops::bn_acc_bytes(C));
+    l.bacc = c.take(ops::bias_acc_bytes(C));
+    l.sums = c.pack(2 * (size_t)C * sizeof(float));
+    l.total = c.off;
+    return l;
 }
+int64_t hlmc_op_bn_bwd_workspace(int C) { return C <= 0 ? 0 : (int64_t)bn_bwd_layout(C).total; }
 int hlmc_op_bn_bwd(void* stream, int dtype, const void* da, const void* y, int64_t R, int C, const float* mean,
                    const float* invstd, const float* gamma, const float* beta, void* dy, float* dgamma, float* dbeta,
                    float* dbias, void* ws, int64_t ws_bytes) {
@@ -579,11 +587,11 @@ int hlmc_op_bn_bwd(void* stream, int dtype, const void* da, const void* y, int64
     HLMC_TRY(device_status_ok());
     hipStream_t s = S(stream);
     unsigned char* w = static_cast<unsigned char*>(ws);
-    const size_t o1 = (ops::bn_acc_bytes(C) + 255) & ~(size_t)255, o2 = o1 + ((ops::bias_acc_bytes(C) + 255) & ~(size_t)255);
-    HLMC_HIP(hipMemsetAsync(ws, 0, o2, s));
-    XAcc mom{reinterpret_cast<unsigned long long*>(w), xacc_shards(C), 2 * C};
-    XAcc bacc{reinterpret_cast<unsigned long long*>(w + o1), xacc_shards(C), C};
-    float* sums = reinterpret_cast<float*>(w + o2);
+    const BnBwdLayout l = bn_bwd_layout(C);
+    HLMC_HIP(hipMemsetAsync(ws, 0, l.sums, s));
+    XAcc mom{reinterpret_cast<unsigned long long*>(w + l.mom), xacc_shards(C), 2 * C};
+    XAcc bacc{reinterpret_cast<unsigned long long*>(w + l.bacc), xacc_shards(C), C};
+    float* sums = reinterpret_cast<float*>(w + l.sums);
     return DT_DISPATCH(dtype,
         ops::bn_act_bwd<float>(s, (const float*)da, C, (const float*)y, R, C, mean, invstd, gamma, beta, 0, nullptr,
                                1.f, (float*)dy, dgamma, dbeta, mom, nullptr, dbias ? bacc : XAcc{}, dbias, sums),
@@ -594,10 +602,17 @@ int hlmc_op_bn_bwd(void* stream, int dtype, const void* da, const void* y, int64
 // the layer below's BatchNorm + LeakyReLU(0.01) applied while the input is staged (the engine's BnInput path):
 // x is then the pre-BN map, whose exact statistics this entry first accumulates with the moments pass the engine's
 // producers would have delivered.  out_sums[2 Co] = (sum y | sum y^2) over the stored bf16 outputs.
-static size_t halo_acc_off(int Ci) { return (XAcc::bytes(xacc_shards(Ci), 2 * Ci) + 255) & ~(size_t)255; }
-int64_t hlmc_op_halo_workspace(int Ci, int Co) {
-    return (int64_t)(halo_acc_off(Ci) + XAcc::bytes(xacc_shards(Co), 2 * Co));
+// workspace: the input map's moments accumulator ain | the output statistics accumulator aout (packed: unrounded total)
+struct HaloLayout { size_t ain, aout, total; };
+static HaloLayout halo_layout(int Ci, int Co) {
+    HaloLayout l;
+    Carver c;
+    l.ain = c.take(XAcc::bytes(xacc_shards(Ci), 2 * Ci));
+    l.aout = c.pack(XAcc::bytes(xacc_shards(Co), 2 * Co));
+    l.total = c.off;
+    return l;
 }
+int64_t hlmc_op_halo_workspace(int Ci, int Co) { return (int64_t)halo_layout(Ci, Co).total; }
 int hlmc_op_halo_fwd(void* stream, int kind, const void* x, int B, int Hi, int Wi, int Ci, const void* wp,
                      const float* bias, int Co, void* y, double* out_sums, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps,
@@ -611,9 +626,10 @@ int hlmc_op_halo_fwd(void* stream, int kind, const void* x, int B, int Hi, int W
     if (xin) HLMC_CHECK_ARG(beta && mean_out && invstd_out && a_out, "hlmc_op_halo_fwd: input BatchNorm arguments");
     hipStream_t s = S(stream);
     unsigned char* w = static_cast<unsigned char*>(ws);
-    XAcc ain{reinterpret_cast<unsigned long long*>(w), xacc_shards(Ci), 2 * Ci};
-    XAcc aout{reinterpret_cast<unsigned long long*>(w + halo_acc_off(Ci)), xacc_shards(Co), 2 * Co};
-    HLMC_HIP(hipMemsetAsync(ws, 0, (size_t)hlmc_op_halo_workspace(Ci, Co), s));
+    const HaloLayout l = halo_layout(Ci, Co);
+    XAcc ain{reinterpret_cast<unsigned long long*>(w + l.ain), xacc_shards(Ci), 2 * Ci};
+    XAcc aout{reinterpret_cast<unsigned long long*>(w + l.aout), xacc_shards(Co), 2 * Co};
+    HLMC_HIP(hipMemsetAsync(ws, 0, l.total, s));
     const int64_t R = (int64_t)B * Hi * Wi;
     ops::BnInput bi{};
     if (xin) {

@@ -510,7 +510,6 @@ class NetT : public NetBase {
         size_t xf = 0, xb = 0, xbias = 0;  // offsets in the forward / backward accumulator regions
         int C = 0;
     };
-    static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
     BnBufs bn_plan(Arena& A, int C) {
         BnBufs b;
         b.C = C;
@@ -518,11 +517,11 @@ class NetT : public NetBase {
         b.inv = A.take(C * 4);
         b.sums = A.take(2 * C * 4);
         b.xf = xf_total;
-        xf_total += al256(ops::bn_acc_bytes(C));
+        xf_total += align256(ops::bn_acc_bytes(C));
         b.xb = xb_total;
-        xb_total += al256(ops::bn_acc_bytes(C));
+        xb_total += align256(ops::bn_acc_bytes(C));
         b.xbias = xb_total;
-        xb_total += al256(ops::bias_acc_bytes(C));
+        xb_total += align256(ops::bias_acc_bytes(C));
         return b;
     }
     XAcc acc_at(size_t off, int C, int ncols) const {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "ops.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 
@@ -23,7 +24,7 @@ struct Arena {
     size_t used = 0;
     size_t take(size_t bytes) {
         size_t o = used;
-        used += (bytes + 255) & ~size_t(255);
+        used += align256(bytes);
         return o;
     }
 };

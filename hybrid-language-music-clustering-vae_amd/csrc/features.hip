@@ -12,11 +12,9 @@
 #include <vector>
 
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
-
-
-
 namespace {
 
 // ---------------------------------------------------------------- librosa.filters.mel (host, double)
@@ -1029,10 +1027,18 @@ void plan_destroy(MelPlanImpl* p) {
 
 int64_t frames(const MelPlanImpl* p, int64_t n) { return 1 + n / p->hop; }
 
-// workspace: mel power [B][n_mels][T] f32 + clip max/min
-int64_t workspace(const MelPlanImpl* p, int64_t B, int64_t n) {
-    return ((B * p->n_mels * frames(p, n) * 4 + 255) & ~int64_t(255)) + 2 * ((B * 4 + 255) & ~int64_t(255));
+// workspace of mel_db / mel_db_zscore / mfcc: mel power S [B][n_mels][T] f32 | clip max [B] | clip min [B]
+struct MelLayout { size_t S, cmax, cmin, total; };
+static MelLayout mel_layout(const MelPlanImpl* p, int64_t B, int64_t n) {
+    MelLayout l;
+    Carver c;
+    l.S = c.take((size_t)(B * p->n_mels * frames(p, n) * 4));
+    l.cmax = c.take((size_t)(B * 4));
+    l.cmin = c.take((size_t)(B * 4));
+    l.total = c.off;
+    return l;
 }
+int64_t workspace(const MelPlanImpl* p, int64_t B, int64_t n) { return (int64_t)mel_layout(p, B, n).total; }
 
 // Persistent grid of the STFT kernels: resident blocks over all CUs (a multiple of 8, one share per XCD), at most
 // one per item rounded up to the XCD count.  The test hook replaces it by a given multiple of 8 (any such grid
@@ -1091,6 +1097,18 @@ static int mel_power(const MelPlanImpl* p, hipStream_t s, const float* pcm, int6
     return HLMC_OK;
 }
 
+// the mel power (T frames) into the workspace's S, the clip max / min into the words behind it (mel_layout)
+struct MelWs { int T; float* S; unsigned *cmax, *cmin; };
+static int mel_power_ws(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t B, int64_t n, void* ws, MelWs* m) {
+    const MelLayout l = mel_layout(p, B, n);
+    char* w = reinterpret_cast<char*>(ws);
+    *m = MelWs{(int)frames(p, n), reinterpret_cast<float*>(w + l.S), reinterpret_cast<unsigned*>(w + l.cmax),
+               reinterpret_cast<unsigned*>(w + l.cmin)};
+    return mel_power(p, s, pcm, B, n, m->S, m->cmax, m->cmin);
+}
+
+// The power goes to `out`, so the workspace holds the two clip words only, packed: include/hlmc.h promises callers
+// that 8 * batch bytes suffice, which mel_layout's offsets (behind an S this entry does not have) would overrun.
 int melspectrogram(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t B, int64_t n, float* out, void* ws) {
     HLMC_CHECK_ARG(ws, "workspace required");
     unsigned* c = reinterpret_cast<unsigned*>(ws);  // clip max / min scratch (2*B words)
@@ -1100,20 +1118,15 @@ int melspectrogram(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_
 int mel_db(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t B, int64_t n, int64_t t_keep, float amin,
            float top_db, float* out, void* ws) {
     HLMC_CHECK_ARG(ws, "workspace required");
-    const int T = (int)frames(p, n);
-    char* w = reinterpret_cast<char*>(ws);
-    float* S = reinterpret_cast<float*>(w);
-    const int64_t sb = (B * p->n_mels * T * 4 + 255) & ~int64_t(255);
-    unsigned* cmax = reinterpret_cast<unsigned*>(w + sb);
-    unsigned* cmin = reinterpret_cast<unsigned*>(w + sb + ((B * 4 + 255) & ~int64_t(255)));
-    HLMC_TRY(mel_power(p, s, pcm, B, n, S, cmax, cmin));
+    MelWs m;
+    HLMC_TRY(mel_power_ws(p, s, pcm, B, n, ws, &m));
     const int64_t tot = B * p->n_mels * t_keep;
     if (t_keep % 4 == 0 && ((uintptr_t)out & 15) == 0)
-        mel_db_kernel<false, float><<<gridn(tot / 4), 256, 0, s>>>(S, (int)B, p->n_mels, T, (int)t_keep, cmax, cmin,
-                                                                   amin, top_db, nullptr, nullptr, out);
+        mel_db_kernel<false, float><<<gridn(tot / 4), 256, 0, s>>>(m.S, (int)B, p->n_mels, m.T, (int)t_keep, m.cmax,
+                                                                   m.cmin, amin, top_db, nullptr, nullptr, out);
     else
-        power_to_db_kernel<<<gridn(tot), 256, 0, s>>>(S, (int)B, p->n_mels, T, (int)t_keep, cmax, cmin, 1, 1.f, amin,
-                                                       top_db, out);
+        power_to_db_kernel<<<gridn(tot), 256, 0, s>>>(m.S, (int)B, p->n_mels, m.T, (int)t_keep, m.cmax, m.cmin, 1, 1.f,
+                                                       amin, top_db, out);
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
@@ -1124,20 +1137,15 @@ int mel_db_zscore(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t
     HLMC_CHECK_ARG(t_keep > 0 && t_keep % 4 == 0, "t_keep must be a positive multiple of 4");
     HLMC_CHECK_ARG(dtype == HLMC_F32 || dtype == HLMC_BF16, "out dtype f32 or bf16");
     HLMC_CHECK_ARG(((uintptr_t)out & (dtype == HLMC_F32 ? 15 : 7)) == 0, "out must be 16-byte (f32) / 8-byte (bf16) aligned");
-    const int T = (int)frames(p, n);
-    char* w = reinterpret_cast<char*>(ws);
-    float* S = reinterpret_cast<float*>(w);
-    const int64_t sb = (B * p->n_mels * T * 4 + 255) & ~int64_t(255);
-    unsigned* cmax = reinterpret_cast<unsigned*>(w + sb);
-    unsigned* cmin = reinterpret_cast<unsigned*>(w + sb + ((B * 4 + 255) & ~int64_t(255)));
-    HLMC_TRY(mel_power(p, s, pcm, B, n, S, cmax, cmin));
+    MelWs m;
+    HLMC_TRY(mel_power_ws(p, s, pcm, B, n, ws, &m));
     const unsigned g = gridn(B * p->n_mels * t_keep / 4);
     if (dtype == HLMC_BF16)
-        mel_db_kernel<true, bf16><<<g, 256, 0, s>>>(S, (int)B, p->n_mels, T, (int)t_keep, cmax, cmin, amin, top_db,
-                                                    mean, scale, reinterpret_cast<bf16*>(out));
+        mel_db_kernel<true, bf16><<<g, 256, 0, s>>>(m.S, (int)B, p->n_mels, m.T, (int)t_keep, m.cmax, m.cmin, amin,
+                                                    top_db, mean, scale, reinterpret_cast<bf16*>(out));
     else
-        mel_db_kernel<true, float><<<g, 256, 0, s>>>(S, (int)B, p->n_mels, T, (int)t_keep, cmax, cmin, amin, top_db,
-                                                     mean, scale, reinterpret_cast<float*>(out));
+        mel_db_kernel<true, float><<<g, 256, 0, s>>>(m.S, (int)B, p->n_mels, m.T, (int)t_keep, m.cmax, m.cmin, amin,
+                                                     top_db, mean, scale, reinterpret_cast<float*>(out));
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
@@ -1145,15 +1153,10 @@ int mel_db_zscore(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t
 int mfcc(const MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t B, int64_t n, int n_mfcc, const float* dct,
          float amin, float top_db, float* out, void* ws) {
     HLMC_CHECK_ARG(ws && n_mfcc > 0 && n_mfcc <= p->n_mels, "bad mfcc arguments");
-    const int T = (int)frames(p, n);
-    char* w = reinterpret_cast<char*>(ws);
-    float* S = reinterpret_cast<float*>(w);
-    const int64_t sb = (B * p->n_mels * T * 4 + 255) & ~int64_t(255);
-    unsigned* cmax = reinterpret_cast<unsigned*>(w + sb);
-    unsigned* cmin = reinterpret_cast<unsigned*>(w + sb + ((B * 4 + 255) & ~int64_t(255)));
-    HLMC_TRY(mel_power(p, s, pcm, B, n, S, cmax, cmin));
-    dim3 grid((T + 63) / 64, (unsigned)B);
-    mfcc_kernel<<<grid, 256, 0, s>>>(S, p->n_mels, T, cmax, dct, n_mfcc, amin, top_db, out);
+    MelWs m;
+    HLMC_TRY(mel_power_ws(p, s, pcm, B, n, ws, &m));
+    dim3 grid((m.T + 63) / 64, (unsigned)B);
+    mfcc_kernel<<<grid, 256, 0, s>>>(m.S, p->n_mels, m.T, m.cmax, dct, n_mfcc, amin, top_db, out);
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
@@ -1279,28 +1282,38 @@ int chroma_tables(MelPlanImpl* p) {
     return HLMC_OK;
 }
 
-int64_t chroma_workspace(const MelPlanImpl* p, int64_t B, int64_t n) {
+// chroma workspace: power S [B][T][kSRow] f32 | peaks cand [B][T][maxpk] (pitch, mag) | peaks per frame cnt [B][T] |
+// tuning bin tidx [B]
+struct ChromaLayout { int T, maxpk; size_t S, cand, cnt, tidx, total; };
+static ChromaLayout chroma_layout(const MelPlanImpl* p, int64_t B, int64_t n) {
+    ChromaLayout l;
     const int64_t T = frames(p, n);
-    auto al = [](int64_t x) { return (x + 255) & ~int64_t(255); };
-    const int64_t mp = pip_slots(p->sr, p->n_fft);
-    return al(B * T * kSRow * 4) + al(B * T * mp * 8) + al(B * T * 4) + al(B * 4);
+    l.T = (int)T;
+    l.maxpk = pip_slots(p->sr, p->n_fft);
+    Carver c;
+    l.S = c.take((size_t)(B * T * kSRow * 4));
+    l.cand = c.take((size_t)(B * T * l.maxpk * 8));
+    l.cnt = c.take((size_t)(B * T * 4));
+    l.tidx = c.take((size_t)(B * 4));
+    l.total = c.off;
+    return l;
 }
+int64_t chroma_workspace(const MelPlanImpl* p, int64_t B, int64_t n) { return (int64_t)chroma_layout(p, B, n).total; }
 
 int chroma_stft(MelPlanImpl* p, hipStream_t s, const float* pcm, int64_t B, int64_t n, float* out, double* tuning,
                 void* ws) {
     HLMC_CHECK_ARG(pcm && out && ws && B > 0 && n > 0 && B <= 65535, "bad chroma_stft arguments");
     HLMC_TRY(chroma_tables(p));
-    const int mp = pip_slots(p->sr, p->n_fft);
+    const ChromaLayout l = chroma_layout(p, B, n);
+    const int mp = l.maxpk, T = l.T;
     HLMC_CHECK_ARG(p->pip_kmin >= 1 && p->pip_kmax <= p->n_fft / 2 && (p->pip_kmax - p->pip_kmin + 1) / 2 < mp,
                    "piptrack frequency mask out of range");
-    const int T = (int)frames(p, n);
-    auto al = [](int64_t x) { return (x + 255) & ~int64_t(255); };
     char* w = reinterpret_cast<char*>(ws);
     PipArgs pa;
-    pa.S = reinterpret_cast<float*>(w);
-    pa.cand = reinterpret_cast<float2*>(w + al(B * T * kSRow * 4));
-    pa.cnt = reinterpret_cast<int*>(w + al(B * T * kSRow * 4) + al(B * T * (int64_t)mp * 8));
-    int* tidx = reinterpret_cast<int*>(w + al(B * T * kSRow * 4) + al(B * T * (int64_t)mp * 8) + al(B * T * 4));
+    pa.S = reinterpret_cast<float*>(w + l.S);
+    pa.cand = reinterpret_cast<float2*>(w + l.cand);
+    pa.cnt = reinterpret_cast<int*>(w + l.cnt);
+    int* tidx = reinterpret_cast<int*>(w + l.tidx);
     pa.maxpk = mp;
     pa.kmin = p->pip_kmin;
     pa.kmax = p->pip_kmax;
@@ -1335,15 +1348,27 @@ int row_mean_std(hipStream_t s, const float* x, int64_t rows, int64_t cols, floa
     return HLMC_OK;
 }
 
-static int col_chunks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(256, n / 64)); }
-int64_t colstats_workspace(int64_t n, int64_t cols) { return 2 * (int64_t)col_chunks(n) * cols * 8; }
+// colstats workspace: per-chunk partial sums p0 [chunks][cols] | p1 [chunks][cols], float64, packed
+struct ColstatsLayout { int chunks; size_t p0, p1, total; };
+static ColstatsLayout colstats_layout(int64_t n, int64_t cols) {
+    ColstatsLayout l;
+    l.chunks = (int)std::max<int64_t>(1, std::min<int64_t>(256, n / 64));
+    Carver c;
+    l.p0 = c.pack((size_t)(l.chunks * cols * 8));
+    l.p1 = c.pack((size_t)(l.chunks * cols * 8));
+    l.total = c.off;
+    return l;
+}
+int64_t colstats_workspace(int64_t n, int64_t cols) { return (int64_t)colstats_layout(n, cols).total; }
 
 int colstats(hipStream_t s, const float* x, int64_t n, int64_t cols, const double* mean, double* o0, double* o1, void* ws) {
     HLMC_CHECK_ARG(x && o0 && ws && n > 0 && cols > 0, "bad colstats arguments");
-    const int nc = col_chunks(n);
+    const ColstatsLayout l = colstats_layout(n, cols);
+    const int nc = l.chunks;
     const int64_t rp = (n + nc - 1) / nc;
-    double* p0 = reinterpret_cast<double*>(ws);
-    double* p1 = o1 ? p0 + (int64_t)nc * cols : nullptr;
+    char* w = reinterpret_cast<char*>(ws);
+    double* p0 = reinterpret_cast<double*>(w + l.p0);
+    double* p1 = o1 ? reinterpret_cast<double*>(w + l.p1) : nullptr;
     dim3 g((unsigned)((cols + 255) / 256), nc);
     col_sum_partial_kernel<<<g, 256, 0, s>>>(x, n, cols, rp, mean, p0, p1);
     HLMC_LAUNCHED();

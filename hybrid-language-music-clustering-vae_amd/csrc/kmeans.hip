@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "features.hpp"
+#include "workspace.hpp"
 
 namespace hlmc {
 namespace {
@@ -36,38 +37,6 @@ __device__ __forceinline__ double einsum_sq_f64(Ld ld, int d) {
         a1 = v * v + a1;
     }
     return a0 + a1;
-}
-
-// float32(max(0, (-2 a.x + ||a||^2) + ||x||^2)) in float64 for up to 16 candidate rows a = X[cand[t]]
-// (sklearn _euclidean_distances_upcast: d = -2 * dot; d += XX; d += YY; float32; max 0)
-struct Cand {
-    int64_t idx[16];
-    int n;
-};
-__global__ __launch_bounds__(256) void km_sqdist_kernel(const float* __restrict__ X, int64_t n, int d, Cand cand,
-                                                        float* __restrict__ out) {
-    extern __shared__ double sh[];  // [cand.n][d] + norms
-    double* A = sh;
-    double* An = sh + cand.n * d;
-    for (int i = threadIdx.x; i < cand.n * d; i += blockDim.x) A[i] = (double)X[cand.idx[i / d] * d + (i % d)];
-    __syncthreads();
-    for (int t = threadIdx.x; t < cand.n; t += blockDim.x)
-        An[t] = einsum_sq_f64([&](int c) { return A[t * d + c]; }, d);
-    __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float* xr = X + i * d;
-        const double xx = einsum_sq_f64([&](int c) { return (double)xr[c]; }, d);
-        double dot[16];
-        for (int t = 0; t < cand.n; ++t) dot[t] = 0.0;
-        for (int k = 0; k < d; ++k) {
-            const double v = xr[k];
-            for (int t = 0; t < cand.n; ++t) dot[t] = fma(A[t * d + k], v, dot[t]);
-        }
-        for (int t = 0; t < cand.n; ++t) {
-            const double dd = -2.0 * dot[t] + An[t] + xx;
-            out[t * n + i] = fmaxf((float)dd, 0.f);
-        }
-    }
 }
 
 // E-step, bit-exact to sklearn's lloyd_iter_chunked_dense (oracle/kmeans_oracle.py estep_dist):
@@ -294,27 +263,40 @@ __device__ __forceinline__ uint64_t km_same_label(int lab, int nbits, bool valid
     }
     return eq;
 }
-// hist[tile][c] = rows of cluster c in the tile
-// restart-batched: blockIdx.y = restart, each with its own labels [n] and workspace (km::PartWs)
+// One restart's partition workspace (int32): hist [tiles][k] | base [tiles][k] | off [k + 1] | order [n], packed, the
+// total rounded to 256 bytes (the stride between restarts).
+struct Layout { int tiles; size_t hist, base, off, order, total; };
+Layout layout(int64_t n, int k) {
+    Layout l;
+    l.tiles = (int)((n + kPartTile - 1) / kPartTile);
+    Carver c;
+    l.hist = c.pack((size_t)l.tiles * k * sizeof(int));
+    l.base = c.pack((size_t)l.tiles * k * sizeof(int));
+    l.off = c.pack((size_t)(k + 1) * sizeof(int));
+    l.order = c.pack((size_t)n * sizeof(int));
+    l.total = align256(c.off);
+    return l;
+}
+// restart-batched: each restart has its own labels [n] and its own Layout::total bytes of the workspace.  The device
+// side walks the same packed order from (tiles, k) instead of carrying Layout's four offsets: with the offsets as
+// kernel arguments km_ring_kernel's prologue is 24 bytes shorter, its loops sit elsewhere in their instruction
+// cache lines, and the partitioned sums measured 3 % slower (profiles/r15/ab.txt).
 struct PartWs {
     char* base;
-    int64_t bytes;   // per restart
+    int64_t bytes;   // per restart: Layout::total
     int tiles, k;
     __device__ int* hist(int r) const { return reinterpret_cast<int*>(base + r * bytes); }
     __device__ int* bas(int r) const { return hist(r) + (int64_t)tiles * k; }
     __device__ int* off(int r) const { return bas(r) + (int64_t)tiles * k; }
     __device__ int* order(int r) const { return off(r) + (k + 1); }
 };
-__global__ __launch_bounds__(64) void km_part_hist_kernel(const int32_t* __restrict__ labels, int n, int k, int nbits,
-                                                          PartWs pw, uint64_t active) {
-    const int rs = blockIdx.y;
-    if (!((active >> rs) & 1)) return;
-    labels += (int64_t)rs * n;
-    int* __restrict__ hist = pw.hist(rs);
-    extern __shared__ int cnt[];  // [k]
+// One wave's walk over partition tile blockIdx.x of one restart's labels: the tile's 16 x 64 labels are loaded (-1 past
+// n), then, behind a barrier for the caller's LDS counters, each 64-row group in row order gets
+// body(label, valid, lanes holding the same label, lanes below this one, row).
+template <typename Body>
+__device__ __forceinline__ void km_part_walk(const int32_t* __restrict__ labels, int n, int nbits, Body body) {
     const int lane = threadIdx.x, tile = blockIdx.x;
     const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int c = lane; c < k; c += 64) cnt[c] = 0;
     int lab[kPartTile / 64];
 #pragma unroll
     for (int q = 0; q < kPartTile / 64; ++q) {
@@ -325,18 +307,30 @@ __global__ __launch_bounds__(64) void km_part_hist_kernel(const int32_t* __restr
 #pragma unroll
     for (int q = 0; q < kPartTile / 64; ++q) {
         const bool valid = lab[q] >= 0;
-        const uint64_t eq = km_same_label(lab[q], nbits, valid);
-        if (valid && (eq & lt) == 0) atomicAdd(&cnt[lab[q]], __popcll(eq));   // one add per label, no return
+        body(lab[q], valid, km_same_label(lab[q], nbits, valid), lt, tile * kPartTile + q * 64 + lane);
     }
+}
+// hist[tile][c] = rows of cluster c in the tile; blockIdx.y = restart
+__global__ __launch_bounds__(64) void km_part_hist_kernel(const int32_t* __restrict__ labels, int n, int k, int nbits,
+                                                          PartWs pw, uint64_t active) {
+    const int rs = blockIdx.y;
+    if (!((active >> rs) & 1)) return;
+    int* __restrict__ hist = pw.hist(rs);
+    extern __shared__ int cnt[];  // [k]
+    for (int c = threadIdx.x; c < k; c += 64) cnt[c] = 0;
+    km_part_walk(labels + (int64_t)rs * n, n, nbits, [&](int lab, bool valid, uint64_t eq, uint64_t lt, int) {
+        if (valid && (eq & lt) == 0) atomicAdd(&cnt[lab], __popcll(eq));   // one add per label, no return
+    });
     __syncthreads();
-    for (int c = lane; c < k; c += 64) hist[(int64_t)tile * k + c] = cnt[c];
+    for (int c = threadIdx.x; c < k; c += 64) hist[(int64_t)blockIdx.x * k + c] = cnt[c];
 }
 // base[tile][c] = (rows of clusters < c) + (rows of cluster c in tiles < tile); off[c] = first row of cluster c.
 // 16 waves: per cluster a wave-level scan over the tiles (no block barriers inside), cluster totals in LDS.
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+template <typename V>
+__device__ __forceinline__ V wave_incl_scan(V v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
+        const V t = __shfl_up(v, o, 64);
         if (lane >= o) v += t;
     }
     return v;
@@ -388,29 +382,16 @@ __global__ __launch_bounds__(64) void km_part_scatter_kernel(const int32_t* __re
                                                              int nbits, PartWs pw, uint64_t active) {
     const int rs = blockIdx.y;
     if (!((active >> rs) & 1)) return;
-    labels += (int64_t)rs * n;
     const int* __restrict__ base = pw.bas(rs);
     int* __restrict__ order = pw.order(rs);
     extern __shared__ int cur[];  // [k] next free position per cluster
-    const int lane = threadIdx.x, tile = blockIdx.x;
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int c = lane; c < k; c += 64) cur[c] = base[(int64_t)tile * k + c];
-    int lab[kPartTile / 64];
-#pragma unroll
-    for (int q = 0; q < kPartTile / 64; ++q) {
-        const int row = tile * kPartTile + q * 64 + lane;
-        lab[q] = row < n ? labels[row] : -1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kPartTile / 64; ++q) {
-        const bool valid = lab[q] >= 0;
-        const uint64_t eq = km_same_label(lab[q], nbits, valid);
-        const int b0 = valid ? cur[lab[q]] : 0;
+    for (int c = threadIdx.x; c < k; c += 64) cur[c] = base[(int64_t)blockIdx.x * k + c];
+    km_part_walk(labels + (int64_t)rs * n, n, nbits, [&](int lab, bool valid, uint64_t eq, uint64_t lt, int row) {
+        const int b0 = valid ? cur[lab] : 0;
         __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): every lane's read of cur[] returned (one wave)
-        if (valid && (eq & lt) == 0) cur[lab[q]] = b0 + __popcll(eq);
-        if (valid) order[b0 + __popcll(eq & lt)] = tile * kPartTile + q * 64 + lane;
-    }
+        if (valid && (eq & lt) == 0) cur[lab] = b0 + __popcll(eq);
+        if (valid) order[b0 + __popcll(eq & lt)] = row;
+    });
 }
 constexpr int kRingSlots = 8, kRingLoaders = 15, kRingPitch = 68;   // slot [column][row], rows padded to 68
 __device__ __forceinline__ int lds_acquire(const int* p) {
@@ -529,29 +510,29 @@ __global__ __launch_bounds__(64 * (kRingLoaders + 1)) void km_ring_kernel(
     }
 }
 
-// _euclidean_dense_dense(squared=True): float32 sum of 4-element groups, then the tail
-// restart-batched: blockIdx.y = restart (C + r k d, labels / out + r n)
+// sklearn _euclidean_dense_dense(squared=True): float32 sum of 4-element groups, then the d % 4 tail
+__device__ __forceinline__ float km_euclid_f32(const float* a, const float* b, int d) {
+    float r = 0.f;
+    const int q = d / 4;
+    for (int g = 0; g < q; ++g) {
+        const float d0 = a[4 * g] - b[4 * g], d1 = a[4 * g + 1] - b[4 * g + 1];
+        const float d2 = a[4 * g + 2] - b[4 * g + 2], d3 = a[4 * g + 3] - b[4 * g + 3];
+        r += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+    }
+    for (int c = 4 * q; c < d; ++c) {
+        const float e = a[c] - b[c];
+        r += e * e;
+    }
+    return r;
+}
+// out[i] = km_euclid_f32(X[i], C[labels[i]]); restart-batched: blockIdx.y = restart (C + r k d, labels / out + r n)
 __global__ void km_rowdist_kernel(const float* __restrict__ X, int64_t n, int d, const float* __restrict__ C, int k,
                                   const int32_t* __restrict__ labels, float* __restrict__ out) {
     C += (int64_t)blockIdx.y * k * d;
     labels += (int64_t)blockIdx.y * n;
     out += (int64_t)blockIdx.y * n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float* a = X + i * d;
-        const float* b = C + (int64_t)labels[i] * d;
-        float r = 0.f;
-        const int q = d / 4;
-        for (int g = 0; g < q; ++g) {
-            const float d0 = a[4 * g] - b[4 * g], d1 = a[4 * g + 1] - b[4 * g + 1];
-            const float d2 = a[4 * g + 2] - b[4 * g + 2], d3 = a[4 * g + 3] - b[4 * g + 3];
-            r += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
-        }
-        for (int c = 4 * q; c < d; ++c) {
-            const float e = a[c] - b[c];
-            r += e * e;
-        }
-        out[i] = r;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = km_euclid_f32(X + i * d, C + (int64_t)labels[i] * d, d);
 }
 // float32 sum of v[0..n) in index order: one wave stages 1024 values per round in LDS (coalesced loads,
 // the next round prefetched in registers); lane 0 adds them sequentially from LDS.
@@ -655,12 +636,7 @@ __global__ __launch_bounds__(1024) void km_pp_search_kernel(const float* __restr
     uint64_t open_hi = open;
     for (int64_t q = 0; q < rows && (open | open_hi); ++q) {
         const int64_t i = s0 + q * 64 + l;
-        double x = i < n ? (double)v[i] : 0.0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double y = __shfl_up(x, o, 64);
-            if (l >= o) x += y;
-        }
+        const double x = wave_incl_scan(i < n ? (double)v[i] : 0.0, l);
         const double S = run + x;
         const double B = u2 * ((double)i + h + 8.0) * S;
         for (int t = 0; t < T; ++t) {
@@ -694,10 +670,16 @@ __global__ __launch_bounds__(1024) void km_pp_search_kernel(const float* __restr
 // out[r][t][i] = min(closest_r[i], float32(max(0, (-2 a.x_i + ||a||^2) + ||x_i||^2))) in float64 with
 // a = X[cand[r][t]] (sklearn _euclidean_distances_upcast + np.minimum(closest, dist)); prev == NULL: no minimum
 // (the first centre's distances).  Candidate rows (float64) in LDS; 8 candidates per pass over a row.
+// CandT: the device array k-means++ draws into (const int64_t*), or up to 16 host-chosen rows by value (CandList:
+// km::sqdist_rows, R = 1, prev == NULL) -- one body, so the two give the same bits for the same candidates.
+struct CandList {
+    int64_t idx[16];
+    __device__ int64_t operator[](int t) const { return idx[t]; }
+};
+template <typename CandT>
 __global__ __launch_bounds__(256) void km_pp_dist_kernel(const float* __restrict__ X, int64_t n, int d, int R, int T,
-                                                         const int64_t* __restrict__ cand,
-                                                         const float* __restrict__ prev, int prevT, PpArgs a,
-                                                         float* __restrict__ out) {
+                                                         const CandT cand, const float* __restrict__ prev, int prevT,
+                                                         PpArgs a, float* __restrict__ out) {
     extern __shared__ double sh[];  // [RT][d] + norms [RT]
     const int RT = R * T;
     double* A = sh;
@@ -766,26 +748,8 @@ __global__ __launch_bounds__(256) void km_update_kernel(int k, int d, const floa
         C_new[i] = sums[i] * (float)(1.0 / (double)w[j]);
     }
     __syncthreads();
-    for (int j = threadIdx.x; j < k; j += blockDim.x) {
-        const float* a = C_new + (int64_t)j * d;
-        const float* b = C_old + (int64_t)j * d;
-        float acc = 0.f;
-        const int q = d / 4;
-        for (int g = 0; g < q; ++g) {
-            const float e0 = a[4 * g] - b[4 * g], e1 = a[4 * g + 1] - b[4 * g + 1];
-            const float e2 = a[4 * g + 2] - b[4 * g + 2], e3 = a[4 * g + 3] - b[4 * g + 3];
-            float sg = e0 * e0;
-            sg = sg + e1 * e1;
-            sg = sg + e2 * e2;
-            sg = sg + e3 * e3;
-            acc = acc + sg;
-        }
-        for (int c = 4 * q; c < d; ++c) {
-            const float e = a[c] - b[c];
-            acc = acc + e * e;
-        }
-        info[j] = acc;
-    }
+    for (int j = threadIdx.x; j < k; j += blockDim.x)
+        info[j] = km_euclid_f32(C_new + (int64_t)j * d, C_old + (int64_t)j * d, d);
     if (threadIdx.x == 0) info[k] = 0.f;
 }
 
@@ -807,14 +771,14 @@ int center(hipStream_t s, const float* X, int64_t n, int d, float* mean, float* 
 int sqdist_rows(hipStream_t s, const float* X, int64_t n, int d, const int64_t* cand, int ncand, float* out) {
     HLMC_CHECK_ARG(X && cand && out && ncand >= 1 && ncand <= 16 && d <= 512, "bad km_sqdist_rows arguments");
     HLMC_CHECK_ARG(n > 0 && d > 0, "bad km_sqdist_rows sizes");
-    Cand c{};
-    c.n = ncand;
+    CandList c{};
     for (int t = 0; t < ncand; ++t) {
         HLMC_CHECK_ARG(cand[t] >= 0 && cand[t] < n, "candidate index out of range");
         c.idx[t] = cand[t];
     }
     const size_t sh = ((size_t)ncand * d + ncand) * sizeof(double);
-    km_sqdist_kernel<<<(unsigned)std::min<int64_t>(4096, (n + 255) / 256), 256, sh, s>>>(X, n, d, c, out);
+    km_pp_dist_kernel<CandList><<<(unsigned)std::min<int64_t>(4096, (n + 255) / 256), 256, sh, s>>>(
+        X, n, d, 1, ncand, c, nullptr, 1, PpArgs{}, out);
     HLMC_LAUNCHED();
     return HLMC_OK;
 }
@@ -850,19 +814,17 @@ int sums(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels,
 }
 
 constexpr int64_t kPartMinRows = 4096;
-size_t sums_ws(int64_t n, int k) {
-    const int64_t tiles = (n + kPartTile - 1) / kPartTile;
-    return (((size_t)(2 * tiles * k + (k + 1) + n) * sizeof(int)) + 255) & ~(size_t)255;
-}
+size_t sums_ws(int64_t n, int k) { return layout(n, k).total; }
 int sums_batch(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels, int k, int R, uint64_t active,
                float* sm, float* w, void* ws, size_t ws_bytes) {
     HLMC_CHECK_ARG(X && labels && sm && w && ws && k > 0 && d > 0 && R >= 1 && R <= 64, "bad km_sums_part arguments");
     HLMC_CHECK_ARG(n > 0 && n < (int64_t)1 << 30 && k <= 8192, "bad km_sums_part sizes");
-    HLMC_CHECK_ARG(ws_bytes >= (size_t)R * sums_ws(n, k), "km_sums_part workspace too small");
+    const Layout l = layout(n, k);
+    HLMC_CHECK_ARG(ws_bytes >= (size_t)R * l.total, "km_sums_part workspace too small");
     active &= mask_of(R);
     if (n <= kPartMinRows) return sums_small(s, X, n, d, labels, k, R, active, sm, w);  // one pass beats four here
-    const int tiles = (int)((n + kPartTile - 1) / kPartTile);
-    PartWs pw{static_cast<char*>(ws), (int64_t)sums_ws(n, k), tiles, k};
+    const int tiles = l.tiles;
+    PartWs pw{static_cast<char*>(ws), (int64_t)l.total, tiles, k};
     const size_t klds = (size_t)k * sizeof(int);
     int nbits = 0;
     while ((1 << nbits) < k) ++nbits;
@@ -921,8 +883,8 @@ int pp_dist(hipStream_t s, const float* X, int64_t n, int d, int R, int T, const
             a.best[r] = best[r];
         }
     }
-    km_pp_dist_kernel<<<(unsigned)std::min<int64_t>(4096, (n + 255) / 256), 256, sh, s>>>(X, n, d, R, T, cand, prev,
-                                                                                         prevT, a, out);
+    km_pp_dist_kernel<const int64_t* __restrict__><<<(unsigned)std::min<int64_t>(4096, (n + 255) / 256), 256, sh, s>>>(
+        X, n, d, R, T, cand, prev, prevT, a, out);
     HLMC_LAUNCHED();
     return HLMC_OK;
 }

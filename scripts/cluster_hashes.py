@@ -1,7 +1,9 @@
 """SHA-256 of every output of the clustering / decomposition ops built on the float64 tile and the workspace carver
-(csrc/dbscan.hip, ward.hip, pca.hip, metrics.hip) on seeded inputs at the fixture shapes; with `--ws-only`, every
-*_workspace query over a grid of sizes instead (host functions: no GPU needed).  A refactor of those files must leave
-every line of both listings as it was:
+(csrc/dbscan.hip, ward.hip, pca.hip, metrics.hip) on seeded inputs at the fixture shapes, of the k-means ops
+(csrc/kmeans.hip) and one whole KMeans fit, and of the mel / chroma ops (csrc/features.hip) with their workspace sizes
+(those queries need a plan, and a plan uploads tables); with `--ws-only`, every plan-free *_workspace query over a grid
+of sizes instead (host functions: no GPU needed).  A refactor of those files must leave every line of both listings as
+it was:
     python scripts/cluster_hashes.py [--ws-only] --compare <parent libhlmc.so> <new libhlmc.so> [out.txt]
 runs the listing once per library (HLMC_LIB), each in a child process of its own, writes the first listing with one
 `same` / `DIFFERENT` mark per line and exits non-zero on any difference.  Without --compare it prints the listing of
@@ -32,6 +34,15 @@ def workspace_lines(lib):
     for k in ks:
         for d in ds:
             yield f"ws cluster_scores k={k} d={d}: {lib.hlmc_cluster_scores_workspace(k, d)}"
+    for n in (1, 1023, 1024, 1025, 4097, 100000):
+        for k in (1, 2, 10, 8192):
+            yield f"ws km_sums n={n} k={k}: {lib.hlmc_km_sums_workspace(n, k)}"
+    for c in (1, 32, 64, 96, 512, 0):
+        yield f"ws op_bn_bwd C={c}: {lib.hlmc_op_bn_bwd_workspace(c)}"
+    for ci, co in ((32, 64), (64, 128), (64, 32), (128, 64), (128, 256), (256, 512), (512, 512), (512, 256), (256, 128)):
+        yield f"ws op_halo Ci={ci} Co={co}: {lib.hlmc_op_halo_workspace(ci, co)}"
+    for n, cols in ((1, 1), (63, 7), (64, 7), (129, 3), (16384, 513), (16385, 513), (100000, 16384)):
+        yield f"ws colstats n={n} cols={cols}: {lib.hlmc_colstats_workspace(n, cols)}"
 
 
 def output_lines(lib, L):
@@ -97,7 +108,114 @@ def output_lines(lib, L):
         L.check(lib.hlmc_cluster_scores(L.stream(), X.data_ptr(), n, d, lab.data_ptr(), K, out2.data_ptr(), ws.data_ptr(),
                                         ws.numel()), "hlmc_cluster_scores")
         yield f"cluster_scores {tag} k={K}: out {digest(out2)} ({float(out2[0]):.17g} {float(out2[1]):.17g})"
+    yield from kmeans_lines(lib, L, digest, buf)
+    yield from feature_lines(lib, L, digest, buf)
     torch.cuda.synchronize()
+
+
+def kmeans_lines(lib, L, digest, buf):
+    """The k-means ops one by one (R = 3 restarts where batched) on two seeded problems -- n = 4097 takes the partition
+    path of the sums, d = 65 and d = 3 the d % 4 tails -- then one whole fit at the n = 1336, d = 128 fixture."""
+    import numpy as np
+    import torch
+    import hlmc_amd
+    from tests.golden import fixtures as FX
+    dev, s, R = torch.device("cuda"), L.stream(), 3
+
+    def f32(*shape):
+        return torch.zeros(*shape, dtype=torch.float32, device=dev)
+
+    for n, d, k in ((4097, 65, 5), (700, 3, 70)):
+        rng = np.random.default_rng(31 * n + d + k)
+        tag = f"n={n} d={d} k={k}"
+        X = torch.from_numpy(rng.normal(0.0, 2.0, (n, d)).astype(np.float32)).to(dev)
+        mean, var, Xc = f32(d), f32(d), f32(n, d)
+        L.check(lib.hlmc_km_center(s, X.data_ptr(), n, d, mean.data_ptr(), var.data_ptr(), Xc.data_ptr()), "km_center")
+        yield f"km_center {tag}: mean+var+Xc {digest(mean, var, Xc)}"
+        for ncand in (5, 16):
+            cand = [int(c) for c in rng.integers(0, n, ncand)]
+            out = f32(ncand, n)
+            L.check(lib.hlmc_km_sqdist_rows(s, Xc.data_ptr(), n, d, L.i64_array(cand), ncand, out.data_ptr()),
+                    "km_sqdist_rows")
+            yield f"km_sqdist_rows {tag} ncand={ncand}: out {digest(out)}"
+        T = 4
+        cand = torch.from_numpy(rng.integers(0, n, R * T)).to(dev)
+        first, second = f32(R, T, n), f32(R, T, n)
+        L.check(lib.hlmc_km_pp_dist(s, Xc.data_ptr(), n, d, R, T, cand.data_ptr(), None, 1, None, first.data_ptr()),
+                "km_pp_dist")
+        yield f"km_pp_dist {tag} R={R} T={T} no prev: out {digest(first)}"
+        cand = torch.from_numpy(rng.integers(0, n, R * T)).to(dev)
+        best = (C.c_int32 * R)(1, 3, 0)
+        L.check(lib.hlmc_km_pp_dist(s, Xc.data_ptr(), n, d, R, T, cand.data_ptr(), first.data_ptr(), T, best,
+                                    second.data_ptr()), "km_pp_dist")
+        yield f"km_pp_dist {tag} R={R} T={T} prev: out {digest(second)}"
+        cen = Xc[torch.from_numpy(rng.integers(0, n, R * k)).to(dev)].reshape(R, k, d).contiguous()
+        lab = torch.zeros(R, n, dtype=torch.int32, device=dev)
+        old = torch.zeros(R, n, dtype=torch.int32, device=dev)
+        changed = torch.zeros(R, dtype=torch.int32, device=dev)
+        act = (1 << R) - 1
+        L.check(lib.hlmc_km_assign_batch(s, Xc.data_ptr(), n, d, cen.data_ptr(), k, R, act, lab.data_ptr(),
+                                         old.data_ptr(), changed.data_ptr()), "km_assign_batch")
+        yield f"km_assign_batch {tag} R={R}: labels+changed {digest(lab, changed)}"
+        sums, w = f32(R, k, d), f32(R, k)
+        ws = buf(R * lib.hlmc_km_sums_workspace(n, k))
+        L.check(lib.hlmc_km_sums_batch(s, Xc.data_ptr(), n, d, lab.data_ptr(), k, R, act, sums.data_ptr(), w.data_ptr(),
+                                       ws.data_ptr(), ws.numel()), "km_sums_batch")
+        yield f"km_sums_batch {tag} R={R}: sums+weights {digest(sums, w)}"
+        new, info = f32(R, k, d), f32(R, k + 1)
+        L.check(lib.hlmc_km_update_batch(s, k, d, R, act, sums.data_ptr(), w.data_ptr(), cen.data_ptr(), new.data_ptr(),
+                                         info.data_ptr()), "km_update_batch")
+        yield f"km_update_batch {tag} R={R}: centres+info {digest(new, info)}"
+        inertia, tmp = f32(R), f32(R, n)
+        L.check(lib.hlmc_km_inertia_batch(s, Xc.data_ptr(), n, d, cen.data_ptr(), k, lab.data_ptr(), R,
+                                          inertia.data_ptr(), tmp.data_ptr()), "km_inertia_batch")
+        yield f"km_inertia_batch {tag} R={R}: inertia+rowdist {digest(inertia, tmp)}"
+    km = hlmc_amd.KMeans(10, random_state=42, n_init=10).fit(FX.blobs(1336, 128, 10, seed=1336 + 128 + 10))
+    fit = digest(torch.from_numpy(km.labels_), torch.from_numpy(np.ascontiguousarray(km.cluster_centers_)),
+                 torch.tensor([km.inertia_], dtype=torch.float64))
+    yield f"KMeans(10, random_state=42, n_init=10).fit n=1336 d=128: labels+centres+inertia {fit} (n_iter {km.n_iter_})"
+
+
+def feature_lines(lib, L, digest, buf):
+    """The mel / chroma ops at B = 65, an even and an odd clip length (pair-load and single-load STFT) and the plans
+    n_mels = 128 and 40; then their workspace sizes over a grid."""
+    import numpy as np
+    import torch
+    from hlmc_amd import features as F
+    dev, s, B, keep, n_mfcc = torch.device("cuda"), L.stream(), 65, 20, 20
+    for n_mels in (128, 40):
+        p = F._plan(22050, 2048, 512, n_mels)
+        for n in (8192, 8191):
+            tag = f"B={B} n={n} n_mels={n_mels}"
+            x = (0.3 * torch.randn(B, n, generator=torch.Generator().manual_seed(n + n_mels))).to(dev)
+            T = int(lib.hlmc_mel_frames(p, n))
+            rng = np.random.default_rng(n + n_mels)
+            mean = torch.from_numpy(rng.normal(-40.0, 5.0, n_mels * keep)).to(dev)
+            scale = torch.from_numpy(rng.uniform(0.5, 9.0, n_mels * keep)).to(dev)
+            ws = buf(lib.hlmc_mel_workspace(p, B, n))
+            out = torch.zeros(B, n_mels, T, device=dev)
+            L.check(lib.hlmc_melspectrogram(p, s, x.data_ptr(), B, n, out.data_ptr(), ws.data_ptr()), "melspectrogram")
+            yield f"melspectrogram {tag}: out {digest(out)}"
+            out = torch.zeros(B, n_mels, keep, device=dev)
+            L.check(lib.hlmc_mel_db(p, s, x.data_ptr(), B, n, keep, 1e-10, 80.0, out.data_ptr(), ws.data_ptr()), "mel_db")
+            yield f"mel_db {tag} keep={keep}: out {digest(out)}"
+            for dtype, code in ((torch.float32, L.HLMC_F32), (torch.bfloat16, L.HLMC_BF16)):
+                out = torch.zeros(B, n_mels, keep, dtype=dtype, device=dev)
+                L.check(lib.hlmc_mel_db_zscore(p, s, x.data_ptr(), B, n, keep, 1e-10, 80.0, mean.data_ptr(),
+                                               scale.data_ptr(), code, out.data_ptr(), ws.data_ptr()), "mel_db_zscore")
+                yield f"mel_db_zscore {tag} keep={keep} {str(dtype)[6:]}: out {digest(out)}"
+            out = torch.zeros(B, n_mfcc, T, device=dev)
+            L.check(lib.hlmc_mfcc(p, s, x.data_ptr(), B, n, n_mfcc, out.data_ptr(), ws.data_ptr()), "mfcc")
+            yield f"mfcc {tag} n_mfcc={n_mfcc}: out {digest(out)}"
+            ws = buf(lib.hlmc_chroma_workspace(p, B, n))
+            out, tun = torch.zeros(B, 12, T, device=dev), torch.zeros(B, dtype=torch.float64, device=dev)
+            L.check(lib.hlmc_chroma_stft(p, s, x.data_ptr(), B, n, out.data_ptr(), tun.data_ptr(), ws.data_ptr()),
+                    "chroma_stft")
+            yield f"chroma_stft {tag}: out+tuning {digest(out, tun)}"
+        for b in (1, 3, 64, 65, 256):
+            for n in (8191, 8192, 65024):
+                yield (f"ws mel B={b} n={n} n_mels={n_mels}: {lib.hlmc_mel_workspace(p, b, n)}  "
+                       f"chroma: {lib.hlmc_chroma_workspace(p, b, n)}")
 
 
 def listing(ws_only):

@@ -91,6 +91,16 @@ def test_sums_reject_bad_arguments():
             dict(base, ws_bytes=ws), part + [(dict(ws_bytes=ws - 1), b"workspace too small")])
 
 
+@pytest.mark.parametrize("k", [1, 2, 10, 8192])
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 4097, 100000])
+def test_sums_workspace_closed_form(n, k):
+    """One restart's partition workspace is the documented carve, int32 and packed -- hist and base [tiles][k] with
+    tiles = ceil(n / 1024), off [k + 1], order [n] -- rounded up to 256 bytes once, at the end."""
+    tiles = -(-n // 1024)
+    packed = 4 * (2 * tiles * k + k + 1 + n)
+    assert L.lib().hlmc_km_sums_workspace(n, k) == -(-packed // 256) * 256
+
+
 def test_update_rejects_bad_arguments():
     _reject(lambda lib, a: lib.hlmc_km_update_batch(None, a["k"], a["d"], a["R"], 1, a["sums"], a["w"], a["C_old"],
                                                     a["C_new"], a["info"]),
