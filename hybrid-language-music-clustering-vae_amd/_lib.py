@@ -96,6 +96,22 @@ _SIGS = {
     "hlmc_op_bn_bwd_workspace": (c_i64, [c_int]),
     "hlmc_op_bn_bwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_i64]),
+    "hlmc_op_bn_act_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp,
+                                   c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_op_bn_fwd_workspace": (c_i64, [c_int]),
+    "hlmc_op_bn_fwd": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_f32, c_vp, c_vp, c_vp,
+                               c_f32, c_f32, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_i64]),
+    "hlmc_op_conv_c1_s2_fused_workspace": (c_i64, [c_int]),
+    "hlmc_op_conv_c1_s2_fused": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_op_latent_workspace": (c_i64, [c_int, c_int, c_int, c_int]),
+    "hlmc_op_heads_reparam": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, C.c_uint64, C.c_uint64, c_vp, c_vp, c_int, C.POINTER(c_int),
+                                      c_vp, c_i64]),
+    "hlmc_op_reparam_bwd_reduce": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp, c_int, C.POINTER(c_int), c_vp, c_i64]),
+    "hlmc_op_linear_wgrad_pair": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                                          c_vp, c_vp, c_i64]),
     "hlmc_km_assign_batch": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_int, C.c_uint64, c_vp, c_vp, c_vp]),
     "hlmc_km_sums_batch": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_int, C.c_uint64, c_vp, c_vp, c_vp, c_i64]),
     "hlmc_km_update_batch": (c_int, [c_vp, c_int, c_int, c_int, C.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -60,6 +60,82 @@ struct hlmc_net {
 
 #define S(stream) reinterpret_cast<hipStream_t>(stream)
 
+// ------------------------------------------------------------------------------------ typed bodies
+// The per-dtype bodies of the op-level BatchNorm / edge-conv / latent entries further down (templates cannot sit
+// inside the extern "C" block).
+struct LatentLayout { size_t slabs, total; };
+template <typename T>
+static int bn_fwd_run(hipStream_t s, int mode, const T* y, int64_t R, int C, const float* gamma, const float* beta,
+                      int act, const uint8_t* mask, float mscale, float* rm, float* rv, int64_t* nbt, float momentum,
+                      float eps, float* mean, float* invstd, T* a, int lda, const ops::FlatOut* fo, int hw, XAcc acc) {
+    switch (mode) {
+    case 0:
+        return ops::bn_act_train<T>(s, y, R, C, acc, false, mean, invstd, rm, rv, nbt, momentum, eps, gamma, beta, act,
+                                    mask, mscale, a, lda, fo, hw);
+    case 1:
+        HLMC_TRY(ops::bn_moments<T>(s, y, R, C, acc));
+        return ops::bn_act_train<T>(s, y, R, C, acc, true, mean, invstd, rm, rv, nbt, momentum, eps, gamma, beta, act,
+                                    mask, mscale, a, lda, fo, hw);
+    case 2:
+        return ops::bn_stats<T>(s, y, R, C, mean, invstd, rm, rv, nbt, momentum, eps, acc);
+    default:
+        HLMC_TRY(ops::bn_eval_stats(s, rm, rv, C, eps, mean, invstd));
+        return ops::bn_act<T>(s, y, R, C, mean, invstd, gamma, beta, act, mask, mscale, a, lda, fo, hw);
+    }
+}
+
+template <typename T>
+static int c1_fused_run(hipStream_t s, int mode, const float* x, int B, int Hi, int Wi, const float* w, const float* bias,
+                        int Co, T* y, double* out_sums, const T* ybn, const float* mean, const float* invstd,
+                        const float* gamma, const float* beta, T* dy_out, float* dgamma, float* dbeta, XAcc acc) {
+    if (mode == 1) {
+        ops::ColStats st{acc, false};
+        HLMC_TRY(ops::conv_c1_s2<T>(s, x, B, Hi, Wi, w, bias, Co, y, &st));
+        HLMC_CHECK_ARG(st.done, "hlmc_op_conv_c1_s2_fused: statistics not delivered by the kernel");
+        return ops::colsum_to_f64(s, acc, 2 * Co, out_sums);
+    }
+    ops::BnBwdFuse bf{ybn, mean, invstd, gamma, beta, acc, false};
+    HLMC_TRY(ops::conv_c1_s2<T>(s, x, B, Hi, Wi, w, bias, Co, y, nullptr, &bf));
+    HLMC_CHECK_ARG(bf.done, "hlmc_op_conv_c1_s2_fused: backward moments not delivered by the kernel");
+    HLMC_TRY(ops::colsum_to_f64(s, acc, 2 * Co, out_sums));
+    if (!dy_out) return HLMC_OK;
+    const int64_t R = (int64_t)B * (Hi / 2) * (Wi / 2);
+    return ops::bn_act_bwd<T>(s, y, Co, ybn, R, Co, mean, invstd, gamma, beta, 0, nullptr, 1.f, dy_out, dgamma, dbeta, acc,
+                              &bf, XAcc{}, nullptr, nullptr);
+}
+
+template <typename T>
+static LatentLayout latent_layout(int B, int K, int L) {
+    LatentLayout l;
+    Carver c;
+    l.slabs = c.take(std::max({ops::linear_partials_ws<T>(B, K, 2 * L), ops::linear_partials_ws<T>(B, K, L),
+                               ops::linear_wgrad_ws<T>(B, 2 * L, K)}));
+    l.total = c.off;
+    return l;
+}
+
+template <typename T>
+static int heads_reparam_run(hipStream_t s, const T* x, int ldx, int B, int K, const T* w, int ldw, int L,
+                             const float* mu_bias, const float* lv_bias, float* mu, float* lv, float* mu_out,
+                             float* lv_out, const float* eps_in, uint64_t seed, uint64_t offset, float* eps_keep, T* z,
+                             int ldz, int* S_out, Ws ws) {
+    int S = 0;
+    HLMC_TRY(ops::linear_partials<T>(s, x, ldx, B, K, w, ldw, 2 * L, ws, &S));
+    if (S_out) *S_out = S;
+    return ops::heads_reparam<T>(s, ws.p, S, B, L, mu_bias, lv_bias, mu, lv, mu_out, lv_out, eps_in, seed, offset,
+                                 eps_keep, z, ldz);
+}
+
+template <typename T>
+static int reparam_bwd_reduce_run(hipStream_t s, const T* x, int ldx, int B, int K, const T* w, int ldw, int L,
+                                  const float* lv, const float* eps, const float* d_mu, const float* d_lv, T* gmu, T* glv,
+                                  int ldg, int* S_out, Ws ws) {
+    int S = 0;
+    HLMC_TRY(ops::linear_partials<T>(s, x, ldx, B, K, w, ldw, L, ws, &S));
+    if (S_out) *S_out = S;
+    return ops::reparam_bwd_reduce<T>(s, ws.p, S, B, L, lv, eps, d_mu, d_lv, gmu, glv, ldg);
+}
+
 extern "C" {
 
 int hlmc_version(void) { return 1; }
@@ -598,6 +674,185 @@ int hlmc_op_bn_bwd(void* stream, int dtype, const void* da, const void* y, int64
         ops::bn_act_bwd<bf16>(s, (const bf16*)da, C, (const bf16*)y, R, C, mean, invstd, gamma, beta, 0, nullptr, 1.f,
                               (bf16*)dy, dgamma, dbeta, mom, nullptr, dbias ? bacc : XAcc{}, dbias, sums));
 }
+// The channel counts the BatchNorm kernels take (kernels.hip check_bn_shape, which every launcher applies again): a row
+// is C / V threads of one 16-byte vector each, a power of two <= 256.  Checked here first so that an entry returns
+// before it touches its workspace.
+static bool bn_shape_ok(int dtype, int C) {
+    const int V = dtype == HLMC_BF16 ? 8 : 4;
+    return C > 0 && C % V == 0 && C / V <= 256 && 256 % (C / V) == 0;
+}
+// The general form of hlmc_op_bn_bwd: any activation, the dropout mask of the dense layers and a gradient row stride
+// above C (bn_act_bwd as the engine's BatchNorm1d and dense layers call it).  Same workspace as hlmc_op_bn_bwd.
+int hlmc_op_bn_act_bwd(void* stream, int dtype, const void* da, int lda, const void* y, int64_t R, int C,
+                       const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
+                       const uint8_t* mask, float mscale, void* dy, float* dgamma, float* dbeta, float* dbias, void* ws,
+                       int64_t ws_bytes) {
+    HLMC_CHECK_ARG(dtype == HLMC_F32 || dtype == HLMC_BF16, "hlmc_op_bn_act_bwd: dtype");
+    HLMC_CHECK_ARG(da && y && mean && invstd && gamma && beta && dy && dgamma && dbeta && ws,
+                   "hlmc_op_bn_act_bwd: NULL argument");
+    HLMC_CHECK_ARG(R >= 1 && act >= 0 && act <= 2, "hlmc_op_bn_act_bwd: R >= 1, act 0 / 1 / 2");
+    HLMC_CHECK_ARG(bn_shape_ok(dtype, C), "hlmc_op_bn_act_bwd: BatchNorm channel count unsupported");
+    HLMC_CHECK_ARG(lda >= C && lda % (dtype == HLMC_BF16 ? 8 : 4) == 0,
+                   "hlmc_op_bn_act_bwd: lda >= C and a multiple of 16 bytes");
+    HLMC_CHECK_ARG(ws_bytes >= hlmc_op_bn_bwd_workspace(C), "hlmc_op_bn_act_bwd: workspace too small");
+    HLMC_TRY(device_status_ok());
+    hipStream_t s = S(stream);
+    unsigned char* w = static_cast<unsigned char*>(ws);
+    const BnBwdLayout l = bn_bwd_layout(C);
+    HLMC_HIP(hipMemsetAsync(ws, 0, l.sums, s));
+    XAcc mom{reinterpret_cast<unsigned long long*>(w + l.mom), xacc_shards(C), 2 * C};
+    XAcc bacc{reinterpret_cast<unsigned long long*>(w + l.bacc), xacc_shards(C), C};
+    float* sums = reinterpret_cast<float*>(w + l.sums);
+    return DT_DISPATCH(dtype,
+        ops::bn_act_bwd<float>(s, (const float*)da, lda, (const float*)y, R, C, mean, invstd, gamma, beta, act, mask,
+                               mscale, (float*)dy, dgamma, dbeta, mom, nullptr, dbias ? bacc : XAcc{}, dbias, sums),
+        ops::bn_act_bwd<bf16>(s, (const bf16*)da, lda, (const bf16*)y, R, C, mean, invstd, gamma, beta, act, mask,
+                              mscale, (bf16*)dy, dgamma, dbeta, mom, nullptr, dbias ? bacc : XAcc{}, dbias, sums));
+}
+
+// BatchNorm forward as the engine runs it.  workspace: the statistics accumulator (2C columns), zeroed here.
+struct BnFwdLayout { size_t acc, total; };
+static BnFwdLayout bn_fwd_layout(int C) {
+    BnFwdLayout l;
+    Carver c;
+    l.acc = c.take(ops::bn_acc_bytes(C));
+    l.total = c.off;
+    return l;
+}
+int64_t hlmc_op_bn_fwd_workspace(int C) { return C <= 0 ? 0 : (int64_t)bn_fwd_layout(C).total; }
+int hlmc_op_bn_fwd(void* stream, int dtype, int mode, const void* y, int64_t R, int C, const float* gamma,
+                   const float* beta, int act, const uint8_t* mask, float mscale, float* running_mean,
+                   float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* mean_out,
+                   float* invstd_out, void* a, int lda, int flat_hw, int flat_ld, double* out_sums, void* ws,
+                   int64_t ws_bytes) {
+    HLMC_CHECK_ARG(dtype == HLMC_F32 || dtype == HLMC_BF16, "hlmc_op_bn_fwd: dtype");
+    HLMC_CHECK_ARG(mode >= 0 && mode <= 3, "hlmc_op_bn_fwd: mode 0 .. 3");
+    HLMC_CHECK_ARG(y && mean_out && invstd_out && ws && R >= 1, "hlmc_op_bn_fwd: NULL argument / R < 1");
+    HLMC_CHECK_ARG(bn_shape_ok(dtype, C), "hlmc_op_bn_fwd: BatchNorm channel count unsupported");
+    HLMC_CHECK_ARG(!running_mean == !running_var, "hlmc_op_bn_fwd: running_mean and running_var come as a pair");
+    HLMC_CHECK_ARG(mode != 3 || (running_mean && !out_sums),
+                   "hlmc_op_bn_fwd: eval mode reads the running statistics and has no batch sums");
+    const bool flat = flat_hw != 0 || flat_ld != 0;
+    if (mode != 2) {
+        HLMC_CHECK_ARG(gamma && beta && a && act >= 0 && act <= 2, "hlmc_op_bn_fwd: gamma / beta / a / act");
+        if (flat) {
+            HLMC_CHECK_ARG(!mask, "hlmc_op_bn_fwd: a flat output takes no mask");
+            HLMC_CHECK_ARG(flat_hw > 0 && R % flat_hw == 0 && R < 2147483647 && flat_ld >= (int64_t)C * flat_hw,
+                           "hlmc_op_bn_fwd: flat output shape");
+        } else {
+            HLMC_CHECK_ARG(lda >= C && lda % (dtype == HLMC_BF16 ? 8 : 4) == 0,
+                           "hlmc_op_bn_fwd: lda >= C and a multiple of 16 bytes");
+        }
+    }
+    HLMC_CHECK_ARG(ws_bytes >= hlmc_op_bn_fwd_workspace(C), "hlmc_op_bn_fwd: workspace too small");
+    hipStream_t s = S(stream);
+    const BnFwdLayout l = bn_fwd_layout(C);
+    HLMC_HIP(hipMemsetAsync(ws, 0, l.total, s));
+    XAcc acc{reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws) + l.acc), xacc_shards(C), 2 * C};
+    const ops::FlatOut fo{flat_ld, nullptr};
+    const ops::FlatOut* fop = flat && mode != 2 ? &fo : nullptr;
+    HLMC_TRY(DT_DISPATCH(dtype,
+        bn_fwd_run<float>(s, mode, (const float*)y, R, C, gamma, beta, act, mask, mscale, running_mean, running_var,
+                          num_batches_tracked, momentum, eps, mean_out, invstd_out, (float*)a, lda, fop, flat_hw, acc),
+        bn_fwd_run<bf16>(s, mode, (const bf16*)y, R, C, gamma, beta, act, mask, mscale, running_mean, running_var,
+                         num_batches_tracked, momentum, eps, mean_out, invstd_out, (bf16*)a, lda, fop, flat_hw, acc)));
+    return out_sums ? ops::colsum_to_f64(s, acc, 2 * C, out_sums) : HLMC_OK;
+}
+
+// The single-channel edge conv in its two statistics-fused modes.  workspace: the exact accumulator (2 x 32 columns)
+// the kernel's blocks add to and, in mode 2, bn_act_bwd's apply pass folds.
+struct C1FusedLayout { size_t acc, total; };
+static C1FusedLayout c1_fused_layout(int Co) {
+    C1FusedLayout l;
+    Carver c;
+    l.acc = c.take(ops::bn_acc_bytes(Co));
+    l.total = c.off;
+    return l;
+}
+int64_t hlmc_op_conv_c1_s2_fused_workspace(int Co) { return Co <= 0 ? 0 : (int64_t)c1_fused_layout(Co).total; }
+int hlmc_op_conv_c1_s2_fused(void* stream, int dtype, int mode, const float* x, int B, int Hi, int Wi, const float* w,
+                             const float* bias, int Co, void* y, double* out_sums, const void* ybn, const float* mean,
+                             const float* invstd, const float* gamma, const float* beta, void* dy_out, float* dgamma,
+                             float* dbeta, void* ws, int64_t ws_bytes) {
+    HLMC_CHECK_ARG(dtype == HLMC_F32 || dtype == HLMC_BF16, "hlmc_op_conv_c1_s2_fused: dtype");
+    HLMC_CHECK_ARG(mode == 1 || mode == 2, "hlmc_op_conv_c1_s2_fused: mode 1 (statistics) or 2 (backward moments)");
+    HLMC_CHECK_ARG(x && w && y && out_sums && ws, "hlmc_op_conv_c1_s2_fused: NULL argument");
+    HLMC_CHECK_ARG(Co == 32, "hlmc_op_conv_c1_s2_fused: only Co == 32");
+    HLMC_CHECK_ARG(B >= 1 && Hi >= 2 && Wi >= 2 && Hi % 2 == 0 && Wi % 2 == 0 &&
+                       (int64_t)B * (Hi / 2) * (Wi / 2) * 8 < ((int64_t)1 << 31),
+                   "hlmc_op_conv_c1_s2_fused: B >= 1, even H / W, fewer than 2^28 output pixels");
+    if (mode == 2) {
+        HLMC_CHECK_ARG(ybn && mean && invstd && gamma && beta, "hlmc_op_conv_c1_s2_fused: mode 2 BatchNorm arguments");
+        HLMC_CHECK_ARG(!dy_out || (dgamma && dbeta), "hlmc_op_conv_c1_s2_fused: dy_out needs dgamma and dbeta");
+        if (dy_out) HLMC_TRY(device_status_ok());
+    }
+    HLMC_CHECK_ARG(ws_bytes >= hlmc_op_conv_c1_s2_fused_workspace(Co), "hlmc_op_conv_c1_s2_fused: workspace too small");
+    hipStream_t s = S(stream);
+    const C1FusedLayout l = c1_fused_layout(Co);
+    HLMC_HIP(hipMemsetAsync(ws, 0, l.total, s));
+    XAcc acc{reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws) + l.acc), xacc_shards(Co), 2 * Co};
+    return DT_DISPATCH(dtype,
+        c1_fused_run<float>(s, mode, x, B, Hi, Wi, w, bias, Co, (float*)y, out_sums, (const float*)ybn, mean, invstd,
+                            gamma, beta, (float*)dy_out, dgamma, dbeta, acc),
+        c1_fused_run<bf16>(s, mode, x, B, Hi, Wi, w, bias, Co, (bf16*)y, out_sums, (const bf16*)ybn, mean, invstd, gamma,
+                           beta, (bf16*)dy_out, dgamma, dbeta, acc));
+}
+
+// The latent reduces.  workspace: the fp32 split-K slabs of the entry's GEMM (one query covers the three entries).
+int64_t hlmc_op_latent_workspace(int dtype, int B, int K, int L) {
+    if (B < 1 || K < 1 || L < 1) return 0;
+    return (int64_t)(dtype == HLMC_BF16 ? latent_layout<bf16>(B, K, L) : latent_layout<float>(B, K, L)).total;
+}
+static int latent_args_ok(const char* who, int dtype, const void* x, int ldx, int B, int K, const void* w, int ldw, int L,
+                          const void* ws, int64_t ws_bytes) {
+    HLMC_CHECK_ARG(dtype == HLMC_F32 || dtype == HLMC_BF16, std::string(who) + ": dtype");
+    HLMC_CHECK_ARG(x && w && ws, std::string(who) + ": NULL argument");
+    HLMC_CHECK_ARG(B >= 1 && K >= 1 && L >= 1 && ldx >= K && ldw >= K, std::string(who) + ": B, K, L >= 1, ld >= K");
+    HLMC_CHECK_ARG(ws_bytes >= hlmc_op_latent_workspace(dtype, B, K, L), std::string(who) + ": workspace too small");
+    return HLMC_OK;
+}
+int hlmc_op_heads_reparam(void* stream, int dtype, const void* x, int ldx, int B, int K, const void* w, int ldw, int L,
+                          const float* mu_bias, const float* lv_bias, float* mu, float* lv, float* mu_out, float* lv_out,
+                          const float* eps_in, uint64_t seed, uint64_t offset, float* eps_keep, void* z, int ldz,
+                          int* S_out, void* ws, int64_t ws_bytes) {
+    HLMC_TRY(latent_args_ok("hlmc_op_heads_reparam", dtype, x, ldx, B, K, w, ldw, L, ws, ws_bytes));
+    HLMC_CHECK_ARG(mu_bias && lv_bias && mu && lv, "hlmc_op_heads_reparam: NULL argument");
+    HLMC_CHECK_ARG(!z || (eps_keep && ldz >= L), "hlmc_op_heads_reparam: z needs eps_keep and ldz >= L");
+    HLMC_CHECK_ARG(offset % 4 == 0, "hlmc_op_heads_reparam: offset must be a multiple of 4");
+    Ws sc{reinterpret_cast<float*>(ws), (size_t)ws_bytes};
+    return DT_DISPATCH(dtype,
+        heads_reparam_run<float>(S(stream), (const float*)x, ldx, B, K, (const float*)w, ldw, L, mu_bias, lv_bias, mu, lv,
+                                 mu_out, lv_out, eps_in, seed, offset, eps_keep, (float*)z, ldz, S_out, sc),
+        heads_reparam_run<bf16>(S(stream), (const bf16*)x, ldx, B, K, (const bf16*)w, ldw, L, mu_bias, lv_bias, mu, lv,
+                                mu_out, lv_out, eps_in, seed, offset, eps_keep, (bf16*)z, ldz, S_out, sc));
+}
+int hlmc_op_reparam_bwd_reduce(void* stream, int dtype, const void* x, int ldx, int B, int K, const void* w, int ldw,
+                               int L, const float* lv, const float* eps, const float* d_mu, const float* d_lv, void* gmu,
+                               void* glv, int ldg, int* S_out, void* ws, int64_t ws_bytes) {
+    HLMC_TRY(latent_args_ok("hlmc_op_reparam_bwd_reduce", dtype, x, ldx, B, K, w, ldw, L, ws, ws_bytes));
+    HLMC_CHECK_ARG(lv && eps && gmu && glv && ldg >= L, "hlmc_op_reparam_bwd_reduce: NULL argument / ldg < L");
+    Ws sc{reinterpret_cast<float*>(ws), (size_t)ws_bytes};
+    return DT_DISPATCH(dtype,
+        reparam_bwd_reduce_run<float>(S(stream), (const float*)x, ldx, B, K, (const float*)w, ldw, L, lv, eps, d_mu, d_lv,
+                                      (float*)gmu, (float*)glv, ldg, S_out, sc),
+        reparam_bwd_reduce_run<bf16>(S(stream), (const bf16*)x, ldx, B, K, (const bf16*)w, ldw, L, lv, eps, d_mu, d_lv,
+                                     (bf16*)gmu, (bf16*)glv, ldg, S_out, sc));
+}
+int hlmc_op_linear_wgrad_pair(void* stream, int dtype, const void* dy, int lddy, const void* x, int ldx, int Mb, int N1,
+                              int K, float* dW1, float* db1, float* dW2, float* db2, void* ws, int64_t ws_bytes) {
+    HLMC_CHECK_ARG(dtype == HLMC_F32 || dtype == HLMC_BF16, "hlmc_op_linear_wgrad_pair: dtype");
+    HLMC_CHECK_ARG(dy && x && dW1 && db1 && dW2 && db2 && ws, "hlmc_op_linear_wgrad_pair: NULL argument");
+    HLMC_CHECK_ARG(Mb >= 1 && N1 >= 1 && K >= 1 && lddy >= 2 * N1 && ldx >= K,
+                   "hlmc_op_linear_wgrad_pair: Mb, N1, K >= 1, lddy >= 2 N1, ldx >= K");
+    HLMC_CHECK_ARG(ws_bytes >= hlmc_op_latent_workspace(dtype, Mb, K, N1), "hlmc_op_linear_wgrad_pair: workspace too small");
+    Ws sc{reinterpret_cast<float*>(ws), (size_t)ws_bytes};
+    return DT_DISPATCH(dtype,
+        ops::linear_wgrad_pair<float>(S(stream), (const float*)dy, lddy, (const float*)x, ldx, Mb, N1, K, dW1, db1, dW2,
+                                      db2, sc),
+        ops::linear_wgrad_pair<bf16>(S(stream), (const bf16*)dy, lddy, (const bf16*)x, ldx, Mb, N1, K, dW1, db1, dW2, db2,
+                                     sc));
+}
+
 // LDS halo-tile forward (conv_s2 / subpixel, bf16) with the train-mode epilogue statistics and, when gamma is given,
 // the layer below's BatchNorm + LeakyReLU(0.01) applied while the input is staged (the engine's BnInput path):
 // x is then the pre-BN map, whose exact statistics this entry first accumulates with the moments pass the engine's

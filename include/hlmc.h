@@ -521,6 +521,67 @@ int64_t hlmc_op_bn_bwd_workspace(int C);
 int hlmc_op_bn_bwd(void* stream, int dtype, const void* da, const void* y, int64_t R, int C, const float* mean,
                    const float* invstd, const float* gamma, const float* beta, void* dy, float* dgamma, float* dbeta,
                    float* dbias, void* ws, int64_t ws_bytes);
+/* hlmc_op_bn_bwd in its general form (bn_act_bwd as the dense and BatchNorm1d layers call it): act 0 LeakyReLU(0.01) /
+ * 1 ReLU / 2 none; mask (nullable, dense [R][C] bytes): dz = da * (mask != 0) * mscale * act'(z), the Dropout behind
+ * the activation; lda >= C: the row stride of da (y and dy are dense).  R >= 1.  With a mask the two-pass form always
+ * runs; without one R <= 1024 runs the one-launch small-layer kernel.  ws: hlmc_op_bn_bwd_workspace(C) bytes. */
+int hlmc_op_bn_act_bwd(void* stream, int dtype, const void* da, int lda, const void* y, int64_t R, int C,
+                       const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
+                       const uint8_t* mask, float mscale, void* dy, float* dgamma, float* dbeta, float* dbias, void* ws,
+                       int64_t ws_bytes);
+/* BatchNorm forward of one [R][C] map y (dtype bf16 / f32), a = act(gamma (y - mean) invstd + beta) [* (mask != 0) *
+ * mscale], act as above, as the engine launches it:
+ *   mode 0  train: moments pass + the activation kernel that finalizes the statistics itself (C <= 512; wider: a
+ *           finalize launch between them);
+ *   mode 1  train: the same with the statistics delivered beforehand (a separate moments launch into the accumulator);
+ *   mode 2  train statistics only (moments + finalize); gamma / beta / a unused;
+ *   mode 3  eval: mean / invstd from running_mean / running_var (required), then the activation.
+ * Train modes write mean_out / invstd_out [C] (biased variance), blend running_mean / running_var (nullable pair;
+ * momentum, unbiased variance; R == 1: the biased value 0) and add 1 to num_batches_tracked (nullable).
+ * a: row stride lda >= C (a multiple of 16 bytes); mask: dense [R][C] bytes.  flat_hw > 0: a is written NCHW-flat
+ * instead, [R / flat_hw][flat_ld] with channel c of pixel p at column c * flat_hw + p (flat_ld >= C * flat_hw; no
+ * mask; lda unused); flat_hw == flat_ld == 0: the NHWC rows.  out_sums (nullable, device f64 [2 C], train modes) =
+ * (sum_rows y | sum_rows y^2) from the exact accumulator.  ws: hlmc_op_bn_fwd_workspace(C) bytes (zeroed here). */
+int64_t hlmc_op_bn_fwd_workspace(int C);
+int hlmc_op_bn_fwd(void* stream, int dtype, int mode, const void* y, int64_t R, int C, const float* gamma,
+                   const float* beta, int act, const uint8_t* mask, float mscale, float* running_mean,
+                   float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* mean_out,
+                   float* invstd_out, void* a, int lda, int flat_hw, int flat_ld, double* out_sums, void* ws,
+                   int64_t ws_bytes);
+/* hlmc_op_conv_c1_s2 (Co == 32) in the two forms that also reduce over its stored output y, as the engine runs them:
+ *   mode 1 (the encoder's input conv): out_sums (device f64 [2 Co]) = (sum y | sum y^2), the next BatchNorm's batch
+ *           statistics, from the kernel's exact accumulator;
+ *   mode 2 (the data gradient of the decoder's output convT; y is then the gradient of the last BatchNorm + LeakyReLU
+ *           layer's output, ybn [B, Hi/2, Wi/2, Co] that layer's pre-BN map with its mean / invstd / gamma / beta):
+ *           out_sums = (sum dz | sum dz xhat), dz = y lrelu'(xhat gamma + beta).  With dy_out (nullable) the
+ *           BatchNorm backward then runs its apply pass alone on those moments (no moments pass): dy_out (dtype),
+ *           dgamma, dbeta [Co].
+ * ws: hlmc_op_conv_c1_s2_fused_workspace(Co) bytes (zeroed here). */
+int64_t hlmc_op_conv_c1_s2_fused_workspace(int Co);
+int hlmc_op_conv_c1_s2_fused(void* stream, int dtype, int mode, const float* x, int B, int Hi, int Wi, const float* w,
+                             const float* bias, int Co, void* y, double* out_sums, const void* ybn, const float* mean,
+                             const float* invstd, const float* gamma, const float* beta, void* dy_out, float* dgamma,
+                             float* dbeta, void* ws, int64_t ws_bytes);
+/* The latent layers' GEMMs whose split-K reduce launch carries the next step's arithmetic.  x [B][ldx] and the weight
+ * w [N][ldw] (N rows of K) in dtype; S_out (nullable, host) receives the split count.  ws: hlmc_op_latent_workspace
+ * bytes (one size serves the three entries at the same B, K, L).
+ *   heads_reparam       w = fc_mu's L rows, then fc_logvar's: mu / lv [B][L] f32 = x w^T + bias, copies mu_out /
+ *                       lv_out (nullable); with z (nullable; dtype, row stride ldz): z = mu + eps exp(lv / 2), eps from
+ *                       eps_in or (NULL) elements offset .. offset + B L of hlmc_randn's stream `seed`, kept in eps_keep
+ *   reparam_bwd_reduce  dz = x w^T (N = L) rounded to dtype; gmu = d_mu + dz, glv = d_lv + dz eps exp(lv / 2) / 2
+ *                       (d_mu / d_lv nullable: 0), dtype, row stride ldg
+ *   linear_wgrad_pair   hlmc_op_linear_wgrad for two layers reading the same x whose dy are the column halves
+ *                       [0, N1) / [N1, 2 N1) of one buffer: one GEMM; ws as for (B = Mb, K, L = N1) */
+int64_t hlmc_op_latent_workspace(int dtype, int B, int K, int L);
+int hlmc_op_heads_reparam(void* stream, int dtype, const void* x, int ldx, int B, int K, const void* w, int ldw, int L,
+                          const float* mu_bias, const float* lv_bias, float* mu, float* lv, float* mu_out, float* lv_out,
+                          const float* eps_in, uint64_t seed, uint64_t offset, float* eps_keep, void* z, int ldz,
+                          int* S_out, void* ws, int64_t ws_bytes);
+int hlmc_op_reparam_bwd_reduce(void* stream, int dtype, const void* x, int ldx, int B, int K, const void* w, int ldw,
+                               int L, const float* lv, const float* eps, const float* d_mu, const float* d_lv, void* gmu,
+                               void* glv, int ldg, int* S_out, void* ws, int64_t ws_bytes);
+int hlmc_op_linear_wgrad_pair(void* stream, int dtype, const void* dy, int lddy, const void* x, int ldx, int Mb, int N1,
+                              int K, float* dW1, float* db1, float* dW2, float* db2, void* ws, int64_t ws_bytes);
 int64_t hlmc_op_halo_workspace(int Ci, int Co);
 int hlmc_op_halo_fwd(void* stream, int kind, const void* x, int B, int Hi, int Wi, int Ci, const void* wp,
                      const float* bias, int Co, void* y, double* out_sums, const float* gamma, const float* beta,

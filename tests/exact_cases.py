@@ -12,6 +12,8 @@ Two checks sharper than a relative L2 norm over the whole tensor:
     absref = the same op on |operands| (with |bias| and |old|), u_out = 2^-8 (bf16: half an ulp, relative) or 2^-24
     (f32).  The second term is the standard K u bound of an f32 sum, doubled (the MFMA's rounding inside its 4- or
     8-term step is not specified)."""
+import math
+
 import torch
 
 TWO24 = float(2 ** 24)
@@ -140,6 +142,28 @@ def exact_case_budgets():
     for B, Hl, Wl in WGRAD_C1_ODD:
         out.append((f"wgrad_c1 odd {(B, Hl, Wl)}", exact_budget(B * Hl * Wl, a, a, 0)))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ guarded outputs
+GUARD = 256
+
+
+class Guarded:
+    """An output tensor `t` with GUARD NaN elements before and after it; NaN-prefilled unless `init` is given."""
+
+    def __init__(self, shape, dtype, device, init=None):
+        n = math.prod(shape)
+        self.buf = torch.full((n + 2 * GUARD,), float("nan"), dtype=dtype, device=device)
+        self.t = self.buf[GUARD:GUARD + n].view(*shape)
+        if init is not None:
+            self.t.copy_(init)
+
+    def check(self, what):
+        lo, hi = self.buf[:GUARD].isnan(), self.buf[-GUARD:].isnan()
+        assert bool(lo.all()) and bool(hi.all()), (
+            f"{what}: store outside the output: {int((~lo).sum())} guard elements before it "
+            f"(offsets {(~lo).nonzero().reshape(-1)[:8].tolist()} of {GUARD}), {int((~hi).sum())} after it "
+            f"(offsets {(~hi).nonzero().reshape(-1)[:8].tolist()})")
 
 
 # ------------------------------------------------------------------------------------------------ comparisons

@@ -12,8 +12,6 @@ random data (assert_elementwise in tests/test_ops_gpu.py) reaches these largest 
 bf16 outputs 0.92 - 0.995 (conv_s2 0.974, subpixel 0.975, halo 0.973, linear 0.987, conv_c1_s2 0.995: the half-ulp
 rounding term is tight), f32 outputs <= 0.093 (wgrad_s2 0.083, linear_wgrad 0.086, wgrad_c1 0.001, convT_c1 0.006);
 the table is in that file's header."""
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -21,11 +19,11 @@ import torch.nn.functional as F
 import hlmc_amd  # noqa: F401  (loads the library)
 from hlmc_amd import _lib as L
 from tests import exact_cases as X
+from tests.exact_cases import Guarded
 
 pytestmark = pytest.mark.gpu
 DT = {"fp32": (L.HLMC_F32, torch.float32), "bf16": (L.HLMC_BF16, torch.bfloat16)}
 WS_BYTES = 512 << 20
-GUARD = 256
 PAD_POISON = 1000.0   # in the ldx / ldw / lddy padding columns: a read past K or N shows
 NT_TILE, LINEAR_TILE, TN_TILE = (128, 64), (64, 64), (32, 128)   # the report's tile grid (gemm_ops.hip with_*_tile)
 NAN = float("nan")
@@ -34,24 +32,6 @@ NAN = float("nan")
 @pytest.fixture(scope="module")
 def ws(cuda):
     return torch.empty(WS_BYTES, dtype=torch.uint8, device=cuda)
-
-
-class Guarded:
-    """An output tensor `t` with GUARD NaN elements before and after it; NaN-prefilled unless `init` is given."""
-
-    def __init__(self, shape, dtype, device, init=None):
-        n = math.prod(shape)
-        self.buf = torch.full((n + 2 * GUARD,), NAN, dtype=dtype, device=device)
-        self.t = self.buf[GUARD:GUARD + n].view(*shape)
-        if init is not None:
-            self.t.copy_(init)
-
-    def check(self, what):
-        lo, hi = self.buf[:GUARD].isnan(), self.buf[-GUARD:].isnan()
-        assert bool(lo.all()) and bool(hi.all()), (
-            f"{what}: store outside the output: {int((~lo).sum())} guard elements before it "
-            f"(offsets {(~lo).nonzero().reshape(-1)[:8].tolist()} of {GUARD}), {int((~hi).sum())} after it "
-            f"(offsets {(~hi).nonzero().reshape(-1)[:8].tolist()})")
 
 
 def seed_of(*dims):
