@@ -6,7 +6,8 @@ Drop-in surface (reference names):
   VAE, vae_loss                                (src/Simple_VAE.py)
   melspectrogram, power_to_db, mfcc, extract_mel_spectrogram, mean_std_pool, StandardScaler
                                                (librosa / sklearn calls of src/1_preprocessing*.py)
-  KMeans                                       (sklearn KMeans calls of the three model scripts)
+  KMeans, kmeans_k_sweep                       (sklearn KMeans calls of the three model scripts and their k = 2..14
+                                                search, all silhouettes in one distance pass)
   DBSCAN, dbscan_eps_sweep                     (sklearn DBSCAN and the eps search of src/Convolutional_VAE.py)
   AgglomerativeClustering, agglomerative_k_sweep   (sklearn's Ward clustering and its k sweep, same script)
   PCA, pca_kmeans_baseline                     (sklearn PCA and the "PCA + KMeans" rows of src/Simple_VAE.py and
@@ -14,6 +15,8 @@ Drop-in surface (reference names):
   TSNE                                         (sklearn t-SNE, the last step of all three scripts, exact repulsion)
   metrics.silhouette_score / davies_bouldin_score / calinski_harabasz_score / adjusted_rand_score /
   normalized_mutual_info_score / calculate_purity   (the sklearn.metrics evaluation calls)
+  silhouette_scores                            (metrics.silhouette_scores: silhouette_score of many labellings of one X,
+                                                each pairwise distance computed once -- what the three sweeps call)
   Adam                                         (torch.optim.Adam of the train loops)
   Trainer                                      (fused train step + RCCL data parallel)
   pipeline.run_pipeline                        (BASELINE config[4]: 30 s clips -> mel -> scaler -> ConvVAE train ->
@@ -21,7 +24,7 @@ Drop-in surface (reference names):
 All compute runs in libhlmc.so (hand-written HIP for gfx950); see include/hlmc.h.
 """
 from . import _lib
-from .cluster import DBSCAN, AgglomerativeClustering, KMeans, agglomerative_k_sweep, dbscan_eps_sweep
+from .cluster import DBSCAN, AgglomerativeClustering, KMeans, agglomerative_k_sweep, dbscan_eps_sweep, kmeans_k_sweep
 from .features import (SPECTRAL_FEATURES, StandardScaler, chroma_stft, extract_mel_spectrogram, extract_spectral_features,
                        mean_std_pool, mel_filterbank, melspectrogram, mfcc, power_to_db, rms, spectral_bandwidth,
                        spectral_centroid, spectral_rolloff, spectral_stats, zero_crossing_rate)
@@ -30,6 +33,7 @@ from . import decomposition
 from .manifold import TSNE
 from . import manifold
 from . import metrics
+from .metrics import silhouette_scores
 from . import preprocess
 from .losses import cvae_loss_function, loss_function, vae_loss
 from .models import VAE, ConditionalVAE, HybridVAE
@@ -39,6 +43,7 @@ from . import pipeline
 
 __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_function", "vae_loss", "melspectrogram",
            "power_to_db", "mfcc", "extract_mel_spectrogram", "mean_std_pool", "mel_filterbank", "StandardScaler",
-           "KMeans", "DBSCAN", "dbscan_eps_sweep", "AgglomerativeClustering", "agglomerative_k_sweep",
+           "KMeans", "kmeans_k_sweep", "silhouette_scores", "DBSCAN", "dbscan_eps_sweep", "AgglomerativeClustering",
+           "agglomerative_k_sweep",
            "PCA", "pca_kmeans_baseline", "TSNE",
            "Adam", "Trainer", "GraphedStep", "metrics"]

@@ -121,6 +121,9 @@ _SIGS = {
     "hlmc_km_inertia_batch": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp]),
     "hlmc_silhouette_workspace": (c_i64, [c_i64, c_int]),
     "hlmc_silhouette": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_i64]),
+    "hlmc_silhouette_batch_workspace": (c_i64, [c_i64, C.POINTER(C.c_int32), c_int]),
+    "hlmc_silhouette_batch": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(C.c_int32), c_int, c_vp, c_vp, c_vp,
+                                      c_i64]),
     "hlmc_cluster_scores_workspace": (c_i64, [c_int, c_int]),
     "hlmc_cluster_scores": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_i64]),
     "hlmc_dbscan_workspace": (c_i64, [c_i64, c_int]),

@@ -26,6 +26,9 @@ its own restarts see the same random numbers as in a single process.  One ``all_
 labels, inertia, centres, n_iter) at the end feeds sklearn's sequential best-of rule in restart order, so the
 result is bit-identical for any world size.
 
+kmeans_k_sweep (after KMeans) is the k = 2..14 search of src/Convolutional_VAE.py:311-329 and src/Simple_VAE.py:244-251:
+X is uploaded and centred once, and the silhouettes of all k come from one metrics.silhouette_scores call.
+
 DBSCAN (end of this file) replaces ``sklearn.cluster.DBSCAN(eps, min_samples=5).fit_predict`` and the eps search at
 src/Convolutional_VAE.py:347-374,382: fp64 MFMA neighbourhoods and union-find labelling on the device.
 
@@ -321,11 +324,16 @@ class KMeans:
         if sample_weight is not None:
             raise ValueError("sample_weight is not supported (the reference never passes it)")
         Xd = self._device_x(X)
-        n, d = Xd.shape
-        if n < self.n_clusters:
-            raise ValueError(f"n_samples={n} should be >= n_clusters={self.n_clusters}")
+        if Xd.shape[0] < self.n_clusters:
+            raise ValueError(f"n_samples={Xd.shape[0]} should be >= n_clusters={self.n_clusters}")
         mean, var, Xc = self._center(Xd)
-        tol = np.mean(var.cpu().numpy()) * self.tol if self.tol else 0.0
+        return self._fit_centered(Xc, mean.cpu().numpy(), var.cpu().numpy())
+
+    def _fit_centered(self, Xc, mean, var):
+        """fit() on the centred device matrix and the host copies of hlmc_km_center's column mean and variance (all
+        three the same for every k: kmeans_k_sweep computes them once).  The caller has checked n >= n_clusters."""
+        n, d = Xc.shape
+        tol = np.mean(var) * self.tol if self.tol else 0.0
         rs = self.random_state if isinstance(self.random_state, np.random.RandomState) \
             else np.random.RandomState(self.random_state)
         n_init = 1 if self.n_init == "auto" else int(self.n_init)
@@ -351,7 +359,7 @@ class KMeans:
         best = self._select_best(runs, self.n_clusters)
         self.labels_ = best[1].astype(np.int32)
         self.inertia_ = best[2]
-        self.cluster_centers_ = best[3] + mean.cpu().numpy()
+        self.cluster_centers_ = best[3] + mean
         self.n_iter_ = best[4]
         self.n_features_in_ = d
         return self
@@ -372,6 +380,37 @@ class KMeans:
         return labels.cpu().numpy()
 
 
+def kmeans_k_sweep(X, k_range=range(2, 15), *, random_state=42, n_init=10, device=None):
+    """The reference's K-Means search (src/Convolutional_VAE.py:311-329, src/Simple_VAE.py:244-251, the one sweep
+    all three scripts share): X is uploaded, validated and centred once for all k, and all silhouettes come from one
+    ``metrics.silhouette_scores`` call (one distance pass per label window instead of one per k).
+
+    Returns ``(best_k, records)``.  ``records[i]`` describes ``k_range[i]``: ``k``, ``labels`` (int32, identical to
+    ``KMeans(k, random_state=random_state, n_init=n_init).fit_predict(X)``), ``inertia`` and ``silhouette`` (the bits
+    of ``metrics.silhouette_score(X, labels)``).  ``best_k`` follows the reference's rule: start at (2, -1) and
+    replace on a strictly greater silhouette."""
+    from . import metrics as M
+    ks = [int(k) for k in k_range]
+    first = KMeans(device=device)
+    Xd = first._device_x(X)
+    n = Xd.shape[0]
+    if any(not 2 <= k <= n - 1 for k in ks):
+        raise ValueError(f"every k must be in [2, n_samples - 1 = {n - 1}] (the silhouette is defined there only)")
+    mean, var, Xc = first._center(Xd)
+    mean, var = mean.cpu().numpy(), var.cpu().numpy()
+    records = []
+    for k in ks:
+        km = KMeans(n_clusters=k, random_state=random_state, n_init=n_init, device=device)._fit_centered(Xc, mean, var)
+        records.append({"k": k, "labels": km.labels_, "inertia": km.inertia_})
+    sils = M.silhouette_scores(Xd, [r["labels"] for r in records]) if records else []
+    best_k, best_sil = 2, -1
+    for rec, sil in zip(records, sils):
+        rec["silhouette"] = sil = float(sil)
+        if sil > best_sil:
+            best_sil, best_k = sil, rec["k"]
+    return best_k, records
+
+
 # ====================================================================================== DBSCAN
 _DBSCAN_WORKSPACE_CAP = 24 << 30   # bytes of bit-packed adjacency held at once by a sweep (17 radii at n = 100,000)
 _DBSCAN_MAX_RADII = 32             # radii per hlmc_dbscan_neighbors call
@@ -384,10 +423,10 @@ def _radius_sq(eps):
     return float(np.float32(e * e))
 
 
-def _dbscan_pass(Xd, eps_list, min_samples, workspace_cap=None):
+def _dbscan_chunks(Xd, eps_list, min_samples, workspace_cap=None):
     """One neighbourhood pass per chunk of radii (as many as the workspace cap holds, at most 32), then the
-    labelling pass per radius.  Yields (index, labels int64 [n], core mask bool [n], borderline pairs) in the
-    order of eps_list; nothing is copied back before a chunk's last launch is queued."""
+    labelling pass per radius.  Yields per chunk the list of its radii's (index, labels int64 [n], core mask bool [n],
+    borderline pairs), in the order of eps_list; nothing is copied back before a chunk's last launch is queued."""
     if min_samples < 1:
         raise ValueError("min_samples must be >= 1")
     eps_list = [float(e) for e in eps_list]
@@ -423,8 +462,13 @@ def _dbscan_pass(Xd, eps_list, min_samples, workspace_cap=None):
             lab_h = labels.cpu().numpy().astype(np.int64)
             core_h = core.cpu().numpy().astype(bool)
             border_h = border.cpu().numpy()
-            for e in range(E):
-                yield c0 + e, lab_h[e], core_h[e], int(border_h[e])
+            yield [(c0 + e, lab_h[e], core_h[e], int(border_h[e])) for e in range(E)]
+
+
+def _dbscan_pass(Xd, eps_list, min_samples, workspace_cap=None):
+    """The radii of _dbscan_chunks one by one."""
+    for grp in _dbscan_chunks(Xd, eps_list, min_samples, workspace_cap):
+        yield from grp
 
 
 class DBSCAN:
@@ -482,16 +526,20 @@ def dbscan_eps_sweep(X, eps_range=np.arange(3.0, 20.0, 1.0), min_samples=5, *, d
     eps_list = [float(e) for e in np.asarray(eps_range, dtype=np.float64).reshape(-1)]
     records = []
     best_eps, best_sil = 5.0, -1
-    for i, labels, core, border in _dbscan_pass(Xd, eps_list, min_samples, workspace_cap):
-        n_clusters = int(labels.max()) + 1 if labels.size else 0
-        n_noise = int((labels == -1).sum())
-        sil = None
-        if n_clusters >= 2:
-            sil = M.silhouette_score(Xd, labels)
-            if sil > best_sil:
-                best_sil, best_eps = sil, eps_list[i]
-        records.append({"eps": eps_list[i], "labels": labels, "n_clusters": n_clusters, "n_noise": n_noise,
-                        "n_borderline_pairs": border, "silhouette": sil})
+    for grp in _dbscan_chunks(Xd, eps_list, min_samples, workspace_cap):
+        scored = []
+        for i, labels, core, border in grp:
+            n_clusters = int(labels.max()) + 1 if labels.size else 0
+            n_noise = int((labels == -1).sum())
+            records.append({"eps": eps_list[i], "labels": labels, "n_clusters": n_clusters, "n_noise": n_noise,
+                            "n_borderline_pairs": border, "silhouette": None})
+            if n_clusters >= 2:
+                scored.append(records[-1])
+        if scored:   # the chunk's qualifying radii in one distance pass, in radius order
+            for rec, sil in zip(scored, M.silhouette_scores(Xd, [r["labels"] for r in scored])):
+                rec["silhouette"] = sil = float(sil)
+                if sil > best_sil:
+                    best_sil, best_eps = sil, rec["eps"]
     if best_sil == -1:
         best_eps = 10.0
     return best_eps, records
@@ -638,12 +686,11 @@ def agglomerative_k_sweep(X, k_range=range(2, 15), *, device=None):
     if any(not 2 <= k <= n - 1 for k in ks):
         raise ValueError(f"every k must be in [2, n_samples - 1 = {n - 1}] (the silhouette is defined there only)")
     children, _ = _ward_tree(Xd)
-    records = []
+    records = [{"k": k, "labels": _ward_cut(children, n, k)} for k in ks]
+    sils = M.silhouette_scores(Xd, [r["labels"] for r in records]) if records else []   # one distance pass for all cuts
     best_k, best_sil = 2, -1
-    for k in ks:
-        labels = _ward_cut(children, n, k)
-        sil = M.silhouette_score(Xd, labels)
+    for rec, sil in zip(records, sils):
+        rec["silhouette"] = sil = float(sil)
         if sil > best_sil:
-            best_sil, best_k = sil, k
-        records.append({"k": k, "labels": labels, "silhouette": sil})
+            best_sil, best_k = sil, rec["k"]
     return best_k, records

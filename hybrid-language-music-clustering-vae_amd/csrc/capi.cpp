@@ -517,6 +517,15 @@ int hlmc_silhouette(void* stream, const float* X, int64_t n, int d, const int32_
                     double* score, void* ws, int64_t ws_bytes) {
     return metrics::silhouette(S(stream), X, n, d, labels, k, samples, score, ws, (size_t)std::max<int64_t>(0, ws_bytes));
 }
+int64_t hlmc_silhouette_batch_workspace(int64_t n, const int32_t* ks, int M) {
+    const size_t b = metrics::silhouette_batch_workspace(n, ks, M);
+    return b ? (int64_t)b : -1;
+}
+int hlmc_silhouette_batch(void* stream, const float* X, int64_t n, int d, const int32_t* labels, const int32_t* ks, int M,
+                          double* samples, double* scores, void* ws, int64_t ws_bytes) {
+    return metrics::silhouette_batch(S(stream), X, n, d, labels, ks, M, samples, scores, ws,
+                                     (size_t)std::max<int64_t>(0, ws_bytes));
+}
 int64_t hlmc_cluster_scores_workspace(int k, int d) { return (int64_t)metrics::cluster_scores_workspace(k, d); }
 int hlmc_cluster_scores(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* out2,
                         void* ws, int64_t ws_bytes) {

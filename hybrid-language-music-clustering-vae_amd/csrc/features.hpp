@@ -87,6 +87,11 @@ namespace metrics {
 size_t silhouette_workspace(int64_t n, int k);
 int silhouette(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels, int k, double* samples,
                double* score, void* ws, size_t ws_bytes);
+// M labellings of one X in one distance pass (labels [M][n], row m in [0, ks[m]); ks is a host array); each
+// labelling's S columns, counts, samples and score have the bits silhouette() gives for it alone
+size_t silhouette_batch_workspace(int64_t n, const int32_t* ks, int M);   // 0: arguments out of range
+int silhouette_batch(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels, const int32_t* ks, int M,
+                     double* samples, double* scores, void* ws, size_t ws_bytes);
 size_t cluster_scores_workspace(int k, int d);
 int cluster_scores(hipStream_t s, const float* X, int64_t n, int d, const int32_t* labels, int k, double* out2,
                    void* ws, size_t ws_bytes);

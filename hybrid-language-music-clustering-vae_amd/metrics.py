@@ -3,6 +3,8 @@
 GPU (libhlmc metrics kernels):
   silhouette_score / silhouette_samples  sklearn.metrics (metric "euclidean"): src/Convolutional_VAE.py:320,
                                          337,361,399; src/Conditional_VAE.py:298; src/Simple_VAE.py:247,256,262
+  silhouette_scores                      the scores of many labellings of one X in one distance pass: the K-Means,
+                                         Ward and DBSCAN parameter searches of src/Convolutional_VAE.py:311-374
   davies_bouldin_score                   src/Convolutional_VAE.py:400
   calinski_harabasz_score                src/Simple_VAE.py:257,263
 Host (label-only contingency arithmetic on n integers, nothing GPU-shaped):
@@ -15,6 +17,7 @@ which is uploaded).
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import numpy as np
@@ -72,6 +75,65 @@ def silhouette_score(X, labels, *, metric="euclidean", sample_size=None, random_
         X = X[torch.as_tensor(idx, device=X.device)] if torch.is_tensor(X) else np.asarray(X)[idx]
         labels = lab[idx]
     return float(_silhouette(X, labels, False)[1].item())
+
+
+# bytes of S [n][K] one hlmc_silhouette_batch call may hold.  The reference's 43 candidates at n = 100,000 take well
+# under 1 GiB together; a DBSCAN labelling of 100,000 rows with 10,000 clusters still fits in one chunk.
+_SILHOUETTE_WORKSPACE_CAP = 8 << 30
+_SILHOUETTE_MAX_BATCH = 64             # labellings per hlmc_silhouette_batch call (include/hlmc.h)
+
+
+def silhouette_scores(X, labelings, *, metric="euclidean", return_samples=False, workspace_cap=None):
+    """``silhouette_score(X, labels)`` for every ``labels`` in ``labelings``, with each pairwise distance computed
+    once for all of them (hlmc_silhouette_batch): a float64 numpy array of ``len(labelings)`` scores, each with the
+    same bits as ``silhouette_score`` gives for that labelling alone.  With ``return_samples`` also the per-sample
+    coefficients, a float64 ``[len(labelings), n]`` tensor on the GPU (row m = ``silhouette_samples(X, labelings[m])``).
+
+    Each labelling may be of any dtype and is encoded with ``np.unique``.  One with fewer than 2 or more than
+    n - 1 labels raises sklearn's ValueError, which names its index.  The labellings are scored in consecutive chunks
+    of at most 64 whose accumulator matrix S (n x the chunk's total number of labels x 8 bytes) stays under
+    ``workspace_cap`` bytes (default 8 GiB); a chunk always holds at least one labelling.  The results do not depend
+    on the chunking."""
+    if metric != "euclidean":
+        raise ValueError("only metric='euclidean' (the reference's) is implemented")
+    x = L.device_matrix(X)
+    n, d = x.shape
+    encs, ks = [], []
+    for m, labels in enumerate(labelings):
+        enc, k = _encode(labels)
+        if enc.shape[0] != n:
+            raise ValueError(f"X has {n} rows but labelling {m} has {enc.shape[0]} entries")
+        if not 2 <= k <= n - 1:  # sklearn check_number_of_labels
+            raise ValueError(f"labelling {m}: Number of labels is {k}. Valid values are 2 to n_samples - 1 (inclusive)")
+        encs.append(enc)
+        ks.append(k)
+    M = len(encs)
+    cap = _SILHOUETTE_WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    chunks, m0 = [], 0
+    while m0 < M:
+        m1, K = m0 + 1, ks[m0]
+        while m1 < M and m1 - m0 < _SILHOUETTE_MAX_BATCH and (K + ks[m1]) * n * 8 <= cap:
+            K += ks[m1]
+            m1 += 1
+        chunks.append((m0, m1))
+        m0 = m1
+    lib = L.lib()
+    with torch.cuda.device(x.device):
+        scores = torch.empty(M, dtype=torch.float64, device=x.device)
+        samples = torch.empty(M, n, dtype=torch.float64, device=x.device) if return_samples else None
+        sized = [((C.c_int32 * (b - a))(*ks[a:b]), a, b) for a, b in chunks]
+        need = [int(lib.hlmc_silhouette_batch_workspace(n, kc, b - a)) for kc, a, b in sized]
+        if any(w <= 0 for w in need):
+            raise ValueError(f"silhouette_scores: n_samples={n} with these label counts is outside the supported range")
+        ws = torch.empty(max(need, default=0), dtype=torch.uint8, device=x.device)
+        for kc, a, b in sized:
+            lab = torch.from_numpy(np.stack(encs[a:b])).to(x.device)
+            L.check(lib.hlmc_silhouette_batch(L.stream(), x.data_ptr(), n, d, lab.data_ptr(), kc, b - a,
+                                              samples[a].data_ptr() if return_samples else None,
+                                              scores[a:].data_ptr(), ws.data_ptr(), ws.numel()),
+                    "hlmc_silhouette_batch")
+        out = scores.cpu().numpy()
+    return (out, samples) if return_samples else out
 
 
 def _cluster_scores(X, labels):

@@ -320,6 +320,24 @@ int hlmc_km_inertia_batch(void* stream, const float* X, int64_t n, int d, const 
 int64_t hlmc_silhouette_workspace(int64_t n, int k);
 int hlmc_silhouette(void* stream, const float* X, int64_t n, int d, const int32_t* labels, int k, double* samples,
                     double* score, void* ws, int64_t ws_bytes);
+/* M labellings of the same X in one distance pass: the K-Means, Ward and DBSCAN parameter searches of
+ * src/Convolutional_VAE.py:311-374 score up to 43 labellings of one latent matrix.  labels: device [M][n] int32, row m
+ * in [0, ks[m]); ks: HOST array [M]; samples (nullable): device [M][n] f64; scores: device [M] f64.  1 <= M <= 64,
+ * every ks[m] in [2, n - 1], n and d as above, and K n 8 bytes must not overflow (else -1 / HLMC_EINVAL).  Label VALUES
+ * are an unchecked precondition, as above.
+ * The labellings form one concatenated label space of K = sum ks[m] columns; labelling m owns the columns
+ * [off_m, off_m + ks[m]), off_m = ks[0] + ... + ks[m - 1].  The distance kernel walks windows of 64 columns (58 for
+ * d > 64: what 160 KB of LDS hold next to the X tile and the labels of the up to kw / 2 + 1 labellings a window of kw
+ * columns overlaps); a labelling may straddle two windows; ||x_i - x_j|| is computed once per window that has j's
+ * label of some labelling inside.  For every labelling m, S[:, off_m : off_m + ks[m]], its counts, samples and score
+ * are bit-identical to hlmc_silhouette on that labelling alone (same per-thread summation order, same arithmetic).
+ * Workspace of hlmc_silhouette_batch (bytes; r256 = round up to 256):
+ *   [0, 8 n K)                 S [n][K] f64, S[i][off_m + c] = sum over rows j with label c in labelling m of ||x_i - x_j||
+ *   [r256(8 n K), + r256(4 K)) counts [K] int32, counts[off_m + c] = rows with label c in labelling m
+ *   then M x 512 f64           block partial sums of the coefficients, labelling m at [512 m, 512 m + 512) */
+int64_t hlmc_silhouette_batch_workspace(int64_t n, const int32_t* ks, int M);
+int hlmc_silhouette_batch(void* stream, const float* X, int64_t n, int d, const int32_t* labels, const int32_t* ks, int M,
+                          double* samples, double* scores, void* ws, int64_t ws_bytes);
 /* out2 (device f64[2]) = { davies_bouldin_score, calinski_harabasz_score } (src/Convolutional_VAE.py:400,
  * src/Simple_VAE.py:257,263), sklearn 1.7 branches included (a centroid distance of 0 contributes 0; all intra
  * distances or all centroid distances within 1e-8 of 0 -> Davies-Bouldin 0; zero intra dispersion -> Calinski-Harabasz
