@@ -19,6 +19,9 @@ Drop-in surface (reference names):
                                                 each pairwise distance computed once -- what the three sweeps call)
   Adam                                         (torch.optim.Adam of the train loops)
   Trainer                                      (fused train step + RCCL data parallel)
+  SimpleAutoencoder, fit_autoencoder, autoencoder_kmeans_baseline, direct_kmeans_baseline
+                                               (the "Autoencoder + K-Means" and "Direct Spectral" rows of
+                                                src/Conditional_VAE.py: the training loop resident on the device)
   pipeline.run_pipeline                        (BASELINE config[4]: 30 s clips -> mel -> scaler -> ConvVAE train ->
                                                 latents -> KMeans, resident in HBM)
 All compute runs in libhlmc.so (hand-written HIP for gfx950); see include/hlmc.h.
@@ -36,9 +39,11 @@ from . import metrics
 from .metrics import silhouette_scores
 from . import preprocess
 from .losses import cvae_loss_function, loss_function, vae_loss
-from .models import VAE, ConditionalVAE, HybridVAE
+from .models import VAE, ConditionalVAE, HybridVAE, SimpleAutoencoder
 from .optim import Adam
-from .train import GraphedStep, Trainer
+from .train import AutoencoderTrainer, GraphedStep, Trainer, dataloader_order, fit_autoencoder
+from . import baselines
+from .baselines import autoencoder_kmeans_baseline, direct_kmeans_baseline
 from . import pipeline
 
 __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_function", "vae_loss", "melspectrogram",
@@ -46,4 +51,5 @@ __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_fun
            "KMeans", "kmeans_k_sweep", "silhouette_scores", "DBSCAN", "dbscan_eps_sweep", "AgglomerativeClustering",
            "agglomerative_k_sweep",
            "PCA", "pca_kmeans_baseline", "TSNE",
-           "Adam", "Trainer", "GraphedStep", "metrics"]
+           "Adam", "Trainer", "GraphedStep", "metrics", "SimpleAutoencoder", "AutoencoderTrainer", "dataloader_order",
+           "fit_autoencoder", "autoencoder_kmeans_baseline", "direct_kmeans_baseline"]

@@ -20,7 +20,7 @@ P_vp = C.POINTER(c_vp)
 P_i64 = C.POINTER(c_i64)
 
 HLMC_F32, HLMC_BF16 = 0, 1
-NET_HYBRID, NET_CVAE, NET_SIMPLE = 0, 1, 2
+NET_HYBRID, NET_CVAE, NET_SIMPLE, NET_AE = 0, 1, 2, 3
 
 _SIGS = {
     "hlmc_version": (c_int, []),
@@ -82,6 +82,9 @@ _SIGS = {
                                    c_vp, c_vp, c_vp]),
     "hlmc_loss_sums_backward": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "hlmc_batch_gather": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
+    "hlmc_mse_rows_workspace": (c_i64, [c_i64, c_i64]),
+    "hlmc_mse_rows": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "hlmc_adam_scratch_bytes": (c_i64, [c_int]),
     "hlmc_adam_step": (c_int, [c_vp, c_int, P_vp, P_vp, P_vp, P_vp, P_i64, c_f32, c_f32, c_f32, c_f32, c_f32,
                                c_int, c_vp]),
@@ -195,7 +198,8 @@ def check_device(what: str = "") -> None:
     st = lib().hlmc_device_status(0)
     if st:
         raise HLMCError(f"{what or 'libhlmc'}: device status {st} (bit 0: BatchNorm backward grid-wide count timed "
-                        f"out; its outputs are NaN) -- clear with hlmc_device_status(1)")
+                        f"out; its outputs are NaN; bit 1: hlmc_batch_gather met a row index outside the data set; that "
+                        f"row is zeros) -- clear with hlmc_device_status(1)")
 
 
 def ptr(t) -> int | None:

@@ -21,6 +21,7 @@ static int device_status_ok() {
     set_error("device status " + std::to_string(st) +
               (st & kDevBnCountTimeout ? ": a one-launch BatchNorm backward's grid-wide arrival count timed out (grid not "
                                          "co-resident); that launch's dgamma / dbeta / dy are NaN" : "") +
+              (st & kDevGatherIndex ? ": hlmc_batch_gather met a row index outside [0, n); that row is zeros" : "") +
               " -- clear with hlmc_device_status(1)");
     return HLMC_EDEVICE;
 }
@@ -355,7 +356,8 @@ int hlmc_net_decode(hlmc_net* h, void* stream, int64_t batch, int train, const f
 }
 int hlmc_net_backward(hlmc_net* h, void* stream, int64_t batch, const float* d_recon, const float* d_recon_text,
                       const float* d_mu, const float* d_logvar, void* ws) {
-    HLMC_CHECK_ARG(h && ws && d_recon && d_mu && d_logvar, "bad arguments");
+    // (the autoencoder has no mu / logvar: AeNet::backward checks its own rules)
+    HLMC_CHECK_ARG(h && ws && d_recon && (h->impl->kind == HLMC_NET_AE || (d_mu && d_logvar)), "bad arguments");
     HLMC_TRY(device_status_ok());
     BackwardArgs a{batch, d_recon, d_recon_text, d_mu, d_logvar, ws};
     return h->impl->backward(S(stream), a);
@@ -426,6 +428,17 @@ int hlmc_net_bucket_wait(hlmc_net* h, int k, void* stream) {
                    "bucket events not recorded (hlmc_net_set_bucket_sync + hlmc_net_backward first)");
     HLMC_HIP(hipStreamWaitEvent(S(stream), ev[k], 0));
     return HLMC_OK;
+}
+
+// ------------------------------------------------------------------------------------ autoencoder feed / loss
+int hlmc_batch_gather(void* stream, const float* X, int64_t n, int d, const int64_t* idx, int count, int B, float* out,
+                      int32_t* valid_dev) {
+    return ae::batch_gather(S(stream), X, n, d, idx, count, B, out, valid_dev);
+}
+int64_t hlmc_mse_rows_workspace(int64_t B, int64_t d) { return (int64_t)ae::mse_rows_workspace(B, d); }
+int hlmc_mse_rows(void* stream, const float* recon, const float* target, int B, int d, const int32_t* valid_dev,
+                  float* d_recon, double* sums2, double* acc, void* ws) {
+    return ae::mse_rows(S(stream), recon, target, B, d, valid_dev, d_recon, sums2, acc, ws);
 }
 
 // ------------------------------------------------------------------------------------ loss / optim

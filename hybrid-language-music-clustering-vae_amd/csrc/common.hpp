@@ -56,7 +56,10 @@ const char* get_error();
 // Faults a kernel detects and reports instead of hanging or returning silently wrong values; the kernel writes the bit
 // with a system-scope store into pinned, mapped host memory (dev_status_word), the host reads it without synchronising
 // (dev_status_take, C ABI hlmc_device_status) and the backward entry points return HLMC_EDEVICE while a bit is raised.
+// Each bit has a 32-bit word of its own in that memory (word i holds bit i), so a kernel raises its bit with a plain
+// store and cannot erase another kernel's; dev_status_take returns the OR of the words.
 constexpr unsigned kDevBnCountTimeout = 1u;   // bn_bwd_fused_kernel: a block's grid-wide arrival spin ran out
+constexpr unsigned kDevGatherIndex = 2u;      // batch_gather_kernel: a row index outside [0, n) (its row is zeros)
 namespace ops {
 unsigned* dev_status_word();
 unsigned dev_status_take(bool clear);

@@ -362,7 +362,7 @@ class NetT : public NetBase {
 
     // ---------------------------------------------------------------- step prologues
     int begin_forward(hipStream_t s, const ForwardArgs& a) {
-        HLMC_CHECK_ARG(a.B >= 2 || !a.train, "BatchNorm in train mode needs batch >= 2");
+        HLMC_CHECK_ARG(a.B >= 2 || !a.train || this->n_bn == 0, "BatchNorm in train mode needs batch >= 2");
         ws_bytes((int)a.B);
         set_ws(a.ws);
         HLMC_TRY(settle(s));
@@ -1379,6 +1379,107 @@ class SimpleNet : public NetT<T> {
     }
 };
 
+// ============================================================================ SimpleAutoencoder (MLP, no BatchNorm)
+// src/Conditional_VAE.py:252-273: Linear(D, 1024) - ReLU - Linear(1024, 256) - ReLU - Linear(256, L) and its mirror.
+// Twelve GEMM launches and two casts per train step, every ReLU in a GEMM epilogue: at the reference's batch of 32 the
+// step is a chain of small dependent launches; its caller can replay it as one captured graph (train.py fit_autoencoder).
+template <typename T>
+class AeNet : public NetT<T> {
+    using Base = NetT<T>;
+    using Base::AT;
+    using Base::P;
+
+  public:
+    static constexpr int H1 = 1024, H2 = 256;
+    int D, L, ldD = 0, ldL = 0;
+    int ew[3], eb[3], dw[3], db[3];
+    size_t x_, h1_, h2_, z_, h3_, h4_, grec_, g4_, g3_, gz_, g2_, g1_;
+
+    AeNet(int input_dim, int latent) : D(input_dim), L(latent) {
+        const int enc[4] = {D, H1, H2, L};
+        for (int i = 0; i < 3; ++i) {
+            ew[i] = this->add_param("encoder." + std::to_string(2 * i) + ".weight", {enc[i + 1], enc[i]});
+            eb[i] = this->add_param("encoder." + std::to_string(2 * i) + ".bias", {enc[i + 1]});
+            this->register_pack(ew[i], 1);
+        }
+        for (int i = 0; i < 3; ++i) {
+            dw[i] = this->add_param("decoder." + std::to_string(2 * i) + ".weight", {enc[2 - i], enc[3 - i]});
+            db[i] = this->add_param("decoder." + std::to_string(2 * i) + ".bias", {enc[2 - i]});
+            this->register_pack(dw[i], 1);
+        }
+        this->finalize_state();
+    }
+
+    void plan(Arena& A, int64_t B) override {
+        const size_t t = sizeof(T);
+        ldD = pad8(D);
+        ldL = pad8(L);
+        x_ = A.take(B * ldD * t);
+        h1_ = A.take(B * H1 * t);
+        h2_ = A.take(B * H2 * t);
+        z_ = A.take(B * ldL * t);
+        h3_ = A.take(B * H2 * t);
+        h4_ = A.take(B * H1 * t);
+        grec_ = A.take(B * ldD * t);
+        g4_ = A.take(B * H1 * t);
+        g3_ = A.take(B * H2 * t);
+        gz_ = A.take(B * ldL * t);
+        g2_ = A.take(B * H2 * t);
+        g1_ = A.take(B * H1 * t);
+        for (int i = 0; i < 3; ++i) {
+            this->lin_need((int)B, ew[i]);
+            this->lin_need((int)B, dw[i]);
+        }
+    }
+
+    int forward(hipStream_t s, const ForwardArgs& a) override {
+        const int B = (int)a.B;
+        HLMC_CHECK_ARG(!a.in1 && !a.in2 && !a.eps && !a.dropout && !a.recon_text && !a.logvar,
+                       "autoencoder: in1, in2 / cond, eps, dropout, recon_text and logvar must be NULL");
+        HLMC_CHECK_ARG(a.in0, "autoencoder: input required");
+        HLMC_CHECK_ARG(a.encode_only ? a.mu != nullptr : (a.recon && !a.mu),
+                       "autoencoder: encode writes z to mu; forward / decode need recon and a NULL mu");
+        HLMC_TRY(this->begin_forward(s, a));
+        if (a.decode_only) {  // decoder(z)
+            HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, L, AT(z_), ldL, B, L));
+        } else {
+            HLMC_TRY(ops::cast2d_from_f32<T>(s, a.in0, D, AT(x_), ldD, B, D));
+            HLMC_TRY(this->template lin_fwd<T>(s, AT(x_), ldD, B, ew[0], eb[0], AT(h1_), H1, 1));
+            HLMC_TRY(this->template lin_fwd<T>(s, AT(h1_), H1, B, ew[1], eb[1], AT(h2_), H2, 1));
+            // z: fp32 to the caller when it asks for it (then cast into the decoder's operand), else the operand itself
+            float* zout = a.encode_only ? a.mu : a.z;
+            if (zout) {
+                HLMC_TRY(this->template lin_fwd<float>(s, AT(h2_), H2, B, ew[2], eb[2], zout, L, 0));
+                if (a.encode_only) return HLMC_OK;
+                HLMC_TRY(ops::cast2d_from_f32<T>(s, zout, L, AT(z_), ldL, B, L));
+            } else {
+                HLMC_TRY(this->template lin_fwd<T>(s, AT(h2_), H2, B, ew[2], eb[2], AT(z_), ldL, 0));
+            }
+        }
+        HLMC_TRY(this->template lin_fwd<T>(s, AT(z_), ldL, B, dw[0], db[0], AT(h3_), H2, 1));
+        HLMC_TRY(this->template lin_fwd<T>(s, AT(h3_), H2, B, dw[1], db[1], AT(h4_), H1, 1));
+        return this->template lin_fwd<float>(s, AT(h4_), H1, B, dw[2], db[2], a.recon, D, 0);
+    }
+
+    int backward(hipStream_t s, const BackwardArgs& a) override {
+        const int B = (int)a.B;
+        HLMC_CHECK_ARG(!a.d_logvar && !a.d_recon_text, "autoencoder: d_logvar and d_recon_text must be NULL");
+        HLMC_TRY(this->begin_backward(s, a));
+        HLMC_TRY(ops::cast2d_from_f32<T>(s, a.d_recon, D, AT(grec_), ldD, B, D));
+        // each data gradient carries the ReLU mask of the layer below in its epilogue (relu_ref: that layer's output)
+        HLMC_TRY(this->lin_bwd(s, AT(grec_), ldD, AT(h4_), H1, B, dw[2], db[2], AT(g4_), H1, 0, AT(h4_)));
+        HLMC_TRY(this->lin_bwd(s, AT(g4_), H1, AT(h3_), H2, B, dw[1], db[1], AT(g3_), H2, 0, AT(h3_)));
+        // the gradient of z: the caller's (a.d_mu, nullable) plus the decoder's; encoder.4 has no activation
+        if (a.d_mu) HLMC_TRY(ops::cast2d_from_f32<T>(s, a.d_mu, L, AT(gz_), ldL, B, L));
+        HLMC_TRY(this->lin_bwd(s, AT(g3_), H2, AT(z_), ldL, B, dw[0], db[0], AT(gz_), ldL, a.d_mu ? 1 : 0));
+        HLMC_TRY(this->lin_bwd(s, AT(gz_), ldL, AT(h2_), H2, B, ew[2], eb[2], AT(g2_), H2, 0, AT(h2_)));
+        HLMC_TRY(this->lin_bwd(s, AT(g2_), H2, AT(h1_), H1, B, ew[1], eb[1], AT(g1_), H1, 0, AT(h1_)));
+        HLMC_TRY(this->lin_bwd(s, AT(g1_), H1, AT(x_), ldD, B, ew[0], eb[0], nullptr, 0));
+        HLMC_TRY(this->wq.join(s));
+        return this->mark(s, 0);
+    }
+};
+
 template <template <typename> class NetTpl, typename... A>
 std::unique_ptr<NetBase> make_typed(int dtype, A... args) {
     if (dtype == HLMC_BF16) return std::unique_ptr<NetBase>(new NetTpl<bf16>(args...));
@@ -1410,6 +1511,11 @@ int make_net(int kind, const int64_t* cfg, int ncfg, int dtype, std::unique_ptr<
             hid.push_back((int)cfg[3 + i]);
         }
         n = make_typed<SimpleNet>(dtype, (int)cfg[0], (int)cfg[1], hid);
+    } else if (kind == HLMC_NET_AE) {
+        HLMC_CHECK_ARG(ncfg == 2, "autoencoder cfg = {input_dim, latent_dim}");
+        HLMC_CHECK_ARG(cfg[0] > 0 && cfg[1] > 0 && cfg[0] <= INT_MAX - 8 && cfg[1] <= INT_MAX - 8,
+                       "autoencoder: input_dim, latent_dim > 0");
+        n = make_typed<AeNet>(dtype, (int)cfg[0], (int)cfg[1]);
     } else {
         HLMC_CHECK_ARG(false, "unknown net kind");
     }

@@ -142,4 +142,14 @@ int run(hipStream_t s, float* Y, float* update, float* gains, int64_t n, const i
         int n_iter, double* stats, void* ws, size_t ws_bytes);
 }  // namespace tsne
 
+// The SimpleAutoencoder train step's feed and loss (autoencoder.hip): the step's rows gathered into a static padded
+// batch with the row count left in device memory, and the mean squared error over that many rows with its gradient.
+namespace ae {
+int batch_gather(hipStream_t s, const float* X, int64_t n, int d, const int64_t* idx, int count, int B, float* out,
+                 int* valid_dev);
+size_t mse_rows_workspace(int64_t B, int64_t d);   // 0: arguments out of range
+int mse_rows(hipStream_t s, const float* recon, const float* target, int B, int d, const int* valid_dev, float* d_recon,
+             double* sums2, double* acc, void* ws);
+}  // namespace ae
+
 }  // namespace hlmc

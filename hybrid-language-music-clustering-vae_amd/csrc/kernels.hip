@@ -1780,7 +1780,10 @@ unsigned* dev_status_word() {
 unsigned dev_status_take(bool clear) {
     unsigned* w = dev_status_word();
     if (!w) return 0;
-    return clear ? __atomic_exchange_n(w, 0u, __ATOMIC_SEQ_CST) : __atomic_load_n(w, __ATOMIC_SEQ_CST);
+    unsigned st = 0;  // word i holds bit i (common.hpp)
+    for (int i = 0; i < 2; ++i)
+        st |= clear ? __atomic_exchange_n(w + i, 0u, __ATOMIC_SEQ_CST) : __atomic_load_n(w + i, __ATOMIC_SEQ_CST);
+    return st;
 }
 
 // Residency of a bn_bwd_fused_kernel instance on one device (blocks per CU x CUs), computed once per (device, kNR,

@@ -172,17 +172,12 @@ class PCA:
         return _project(Zd, B, None, self._mean64)
 
 
-def pca_kmeans_baseline(X, n_components, n_clusters, *, y_true=None, random_state=42, n_init=10, device=None):
-    """The reference's baseline row on the device: PCA -> KMeans -> silhouette and Calinski-Harabasz
-    (src/Simple_VAE.py:258-263), plus NMI, ARI and purity when ``y_true`` is given (``evaluate_clustering`` at
-    src/Conditional_VAE.py:296-308, 422-425).  The PCA features stay on the device between the three stages.
-
-    Returns ``(features, labels, scores)``: the float32 feature tensor on the device, the int32 K-Means labels and a
-    dict keyed as the reference's CSV columns ('Silhouette', 'Calinski-Harabasz'; with ``y_true`` also 'NMI', 'ARI',
-    'Purity')."""
+def kmeans_scores(feats, n_clusters, *, y_true=None, random_state=42, n_init=10):
+    """K-Means on the device features and the reference's scores of its labels: ``(labels, scores)``, scores keyed as
+    the reference's CSV columns ('Silhouette', 'Calinski-Harabasz'; with ``y_true`` also 'NMI', 'ARI', 'Purity').  The
+    evaluation every baseline row shares (``evaluate_clustering`` at src/Conditional_VAE.py:296-308)."""
     from . import metrics as M
     from .cluster import KMeans
-    feats = PCA(n_components=n_components, device=device).fit_transform(X)
     kmeans = KMeans(n_clusters=n_clusters, random_state=random_state, n_init=n_init, device=feats.device)
     labels = kmeans.fit_predict(feats)
     scores = {"Silhouette": M.silhouette_score(feats, labels),
@@ -191,4 +186,17 @@ def pca_kmeans_baseline(X, n_components, n_clusters, *, y_true=None, random_stat
         scores["NMI"] = M.normalized_mutual_info_score(y_true, labels)
         scores["ARI"] = M.adjusted_rand_score(y_true, labels)
         scores["Purity"] = M.calculate_purity(y_true, labels)
+    return labels, scores
+
+
+def pca_kmeans_baseline(X, n_components, n_clusters, *, y_true=None, random_state=42, n_init=10, device=None):
+    """The reference's baseline row on the device: PCA -> KMeans -> silhouette and Calinski-Harabasz
+    (src/Simple_VAE.py:258-263), plus NMI, ARI and purity when ``y_true`` is given (``evaluate_clustering`` at
+    src/Conditional_VAE.py:296-308, 422-425).  The PCA features stay on the device between the three stages.
+
+    Returns ``(features, labels, scores)``: the float32 feature tensor on the device, the int32 K-Means labels and a
+    dict keyed as the reference's CSV columns ('Silhouette', 'Calinski-Harabasz'; with ``y_true`` also 'NMI', 'ARI',
+    'Purity')."""
+    feats = PCA(n_components=n_components, device=device).fit_transform(X)
+    labels, scores = kmeans_scores(feats, n_clusters, y_true=y_true, random_state=random_state, n_init=n_init)
     return feats, labels, scores

@@ -3,6 +3,7 @@
   HybridVAE       — src/Convolutional_VAE.py:75-185
   ConditionalVAE  — src/Conditional_VAE.py:109-231
   VAE             — src/Simple_VAE.py:47-105
+  SimpleAutoencoder — src/Conditional_VAE.py:252-273 (the "Autoencoder + K-Means" baseline: no BatchNorm, no sampling)
 
 Each class registers exactly the reference's submodules (same names, shapes, construction order),
 so ``torch.manual_seed(s); Model(...)`` initialises bit-identical weights and ``state_dict`` files
@@ -138,17 +139,17 @@ class _NetFn(torch.autograd.Function):
         out = owner._alloc_outputs(B, dev)
         L.check(L.lib().hlmc_net_forward(net.h, L.stream(), B, int(train), L.ptr(audio), L.ptr(text), L.ptr(cond),
                                          L.ptr(eps), L.ptr(dropout), L.ptr(out["recon"]), L.ptr(out.get("recon_text")),
-                                         L.ptr(out["mu"]), L.ptr(out["logvar"]), L.ptr(out.get("z")), ws.data_ptr()),
-                "hlmc_net_forward")
+                                         L.ptr(out.get("mu")), L.ptr(out.get("logvar")), L.ptr(out.get("z")),
+                                         ws.data_ptr()), "hlmc_net_forward")
         # the engine's backward re-reads audio (the first conv's weight gradient): keep it alive until then
         ctx.owner, ctx.ws, ctx.B, ctx.audio = owner, ws, B, audio
         ctx.has_text = "recon_text" in out
         ctx.shapes = {k: v.shape for k, v in out.items()}
-        outs = [out["recon"], out.get("recon_text"), out["mu"], out["logvar"], out.get("z")]
-        for o in outs:
-            if o is None:
-                continue
-        ctx.mark_non_differentiable(*[o for o in [out.get("z")] if o is not None])
+        outs = [out["recon"], out.get("recon_text"), out.get("mu"), out.get("logvar"), out.get("z")]
+        # a model without latent heads (SimpleAutoencoder): z = encoder(x) is its latent output, and differentiable
+        ctx.z_is_latent = "mu" not in out
+        if not ctx.z_is_latent:
+            ctx.mark_non_differentiable(*[o for o in [out.get("z")] if o is not None])
         return tuple(o if o is not None else torch.empty(0, device=dev) for o in outs)
 
     @staticmethod
@@ -163,8 +164,10 @@ class _NetFn(torch.autograd.Function):
             return t.contiguous().float()
 
         d_recon = g(d_recon, "recon")
-        d_mu = g(d_mu, "mu")
-        d_lv = g(d_lv, "logvar")
+        if ctx.z_is_latent:  # the engine takes z's upstream gradient in the d_mu slot
+            d_mu, d_lv = g(d_z, "z"), None
+        else:
+            d_mu, d_lv = g(d_mu, "mu"), g(d_lv, "logvar")
         d_rt = g(d_rt, "recon_text") if ctx.has_text else None
         L.check(L.lib().hlmc_net_backward(net.h, L.stream(), ctx.B, L.ptr(d_recon), L.ptr(d_rt), L.ptr(d_mu),
                                           L.ptr(d_lv), ctx.ws.data_ptr()), "hlmc_net_backward")
@@ -178,6 +181,7 @@ class _NativeModule(nn.Module):
     """Shared plumbing: lazily created native net, flat grad buffer, dtype selection."""
 
     _kind = -1
+    _latent_heads = True  # mu / logvar heads and a sampled z (False: SimpleAutoencoder)
 
     def _native_cfg(self):  # pragma: no cover - abstract
         raise NotImplementedError
@@ -249,7 +253,7 @@ class _NativeModule(nn.Module):
 
     def _run(self, audio, text=None, cond=None, eps=None, dropout=None):
         L.require_cuda(audio, text, cond, eps, dropout)
-        if eps is None and audio.is_cuda and torch.cuda.is_current_stream_capturing():
+        if eps is None and self._latent_heads and audio.is_cuda and torch.cuda.is_current_stream_capturing():
             # under torch.cuda.graph capture the engine's host-side Philox offset would freeze into the graph (every
             # replay the same noise): draw it with torch's graph-safe generator instead, as Trainer does
             eps = torch.randn(audio.shape[0], self.latent_dim, device=audio.device)
@@ -261,7 +265,7 @@ class _NativeModule(nn.Module):
         L.require_cuda(in0, in1, in2)
         B = in0.shape[0]
         mu = torch.empty(B, self.latent_dim, device=in0.device)
-        lv = torch.empty_like(mu)
+        lv = torch.empty_like(mu) if self._latent_heads else None
         ws = net.new_workspace(B, in0.device)
         L.check(L.lib().hlmc_net_encode(net.h, L.stream(), B, int(self.training), L.ptr(in0), L.ptr(in1), L.ptr(in2),
                                         L.ptr(mu), L.ptr(lv), ws.data_ptr()), "hlmc_net_encode")
@@ -275,7 +279,7 @@ class _NativeModule(nn.Module):
         B = z.shape[0]
         if z.dim() != 2 or z.shape[1] != self.latent_dim:
             raise ValueError(f"z must be [batch, {self.latent_dim}], got {tuple(z.shape)}")
-        if self.training and B < 2:
+        if self.training and B < 2 and net.n_bn:
             raise ValueError("BatchNorm in train mode needs batch >= 2 (call .eval() to decode one latent)")
         out = self._alloc_outputs(B, z.device)
         ws = net.new_workspace(B, z.device)
@@ -457,3 +461,47 @@ class VAE(_NativeModule):
 
     def get_latent_features(self, x):
         return self.encode(x)[0]
+
+
+class SimpleAutoencoder(_NativeModule):
+    """src/Conditional_VAE.py:252-273: Linear(input_dim, 1024) - ReLU - Linear(1024, 256) - ReLU - Linear(256, latent_dim)
+    and its mirror.  ``forward(x) -> (recon, z)``, differentiable in both, so the reference's loop (mse_loss on recon,
+    Adam) runs unchanged; ``train.fit_autoencoder`` is that loop with the data resident on the device."""
+
+    _kind = L.NET_AE
+    _latent_heads = False
+
+    def __init__(self, input_dim, latent_dim=64, compute_dtype="fp32"):
+        super().__init__()
+        self.input_dim, self.latent_dim = input_dim, latent_dim
+
+        def chain(dims):
+            mods = []
+            for i, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
+                mods.append(nn.Linear(a, b))
+                if i + 2 < len(dims):
+                    mods.append(nn.ReLU())
+            return nn.Sequential(*mods)
+
+        dims = [input_dim, 1024, 256, latent_dim]
+        self.encoder = chain(dims)
+        self.decoder = chain(dims[::-1])
+        self._init_native(compute_dtype)
+
+    def _native_cfg(self):
+        return [self.input_dim, self.latent_dim]
+
+    def _alloc_outputs(self, B, dev):
+        return {"recon": torch.empty(B, self.input_dim, device=dev), "z": torch.empty(B, self.latent_dim, device=dev)}
+
+    def encode(self, x):
+        """z = self.encoder(x), the latents K-Means clusters.  Inference entry: no autograd graph is recorded."""
+        return self._encode_native(x.detach().float().contiguous())[0]
+
+    def decode(self, z):
+        """self.decoder(z).  Inference entry: no autograd graph is recorded."""
+        return self._decode_native(z)["recon"]
+
+    def forward(self, x):
+        recon, _, _, _, z = self._run(x.float().contiguous())
+        return recon, z

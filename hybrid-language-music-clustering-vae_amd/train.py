@@ -25,10 +25,11 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
-from .models import ConditionalVAE, HybridVAE, VAE
+from .models import ConditionalVAE, HybridVAE, SimpleAutoencoder, VAE
 
 
 class Trainer:
@@ -373,3 +374,160 @@ class GraphedStep:
         """Back to eager Trainer.step."""
         self.trainer._graph = False
         self.graph.reset()
+
+
+# ----------------------------------------------------------------------------------------- SimpleAutoencoder
+class AutoencoderTrainer(Trainer):
+    """The train step of the reference's autoencoder baseline (src/Conditional_VAE.py:428-452): forward ->
+    mse_loss(recon, batch) -> backward -> Adam, as four libhlmc calls with no host synchronisation.  Single process.
+
+    ``step(batch, valid)`` treats only the first ``valid`` rows of ``batch`` as data (``valid``: a device int32[1]
+    tensor, as hlmc_batch_gather leaves it; None = every row): the loss is their mean, the gradient rows of the others
+    are exactly zero, so a padded short batch takes the step its rows alone would take -- and because ``valid`` is read
+    on the device, one captured graph (GraphedStep) serves the full and the short batches of an epoch alike.
+    ``loss_acc`` (device float64[1]) grows by every step's loss: a running epoch loss that costs no read-back."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        if not isinstance(model, SimpleAutoencoder):
+            raise TypeError("AutoencoderTrainer trains a SimpleAutoencoder")
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, beta=0.0, text_weight=0.0)
+        self.kind = "ae"
+        self.loss_acc = torch.zeros(1, dtype=torch.float64, device=self.device)
+
+    def _buffers(self, B):
+        if B not in self._cache:
+            dev, D = self.device, self.model.input_dim
+            lws = max(256, int(L.lib().hlmc_mse_rows_workspace(B, D)))
+            self._cache[B] = dict(recon=torch.empty(B, D, device=dev), d_recon=torch.empty(B, D, device=dev),
+                                  ws=self.net.new_workspace(B, dev), lws=torch.empty(lws, dtype=torch.uint8, device=dev),
+                                  sums=torch.zeros(2, dtype=torch.float64, device=dev),
+                                  full=torch.full((1,), B, dtype=torch.int32, device=dev))
+        return self._cache[B]
+
+    def step(self, batch, valid=None):
+        """One optimisation step; returns the device float64[2] {sum of squared errors over the valid rows, their
+        element count} (``loss`` turns it into the reference's ``loss.item()``)."""
+        lib, s = L.lib(), L.stream()
+        L.require_cuda(batch, valid)
+        B, D = batch.shape
+        if D != self.model.input_dim or batch.dtype != torch.float32:
+            raise ValueError(f"batch must be float32 [rows, {self.model.input_dim}], got {tuple(batch.shape)} {batch.dtype}")
+        if valid is not None and (valid.dtype != torch.int32 or valid.numel() != 1):
+            raise ValueError("valid must be a device int32 tensor of one element")
+        c = self._buffers(B)
+        L.check(lib.hlmc_net_forward(self.net.h, s, B, 1, L.ptr(batch), None, None, None, None, L.ptr(c["recon"]), None,
+                                     None, None, None, c["ws"].data_ptr()), "hlmc_net_forward")
+        L.check(lib.hlmc_mse_rows(s, L.ptr(c["recon"]), L.ptr(batch), B, D, L.ptr(c["full"] if valid is None else valid),
+                                  L.ptr(c["d_recon"]), c["sums"].data_ptr(), self.loss_acc.data_ptr(),
+                                  c["lws"].data_ptr()), "hlmc_mse_rows")
+        L.check(lib.hlmc_net_backward(self.net.h, s, B, L.ptr(c["d_recon"]), None, None, None, c["ws"].data_ptr()),
+                "hlmc_net_backward")
+        if self._graph:  # coefficients staged by prepare_step_coefficients()
+            L.check(lib.hlmc_net_adam_step_dev(self.net.h, s, *self._mv, self._coef_dev.data_ptr()),
+                    "hlmc_net_adam_step_dev")
+            return c["sums"]
+        self.step_count += 1
+        b1, b2 = self.betas
+        L.check(lib.hlmc_net_adam_step(self.net.h, s, *self._mv, float(self.lr), float(b1), float(b2), float(self.eps),
+                                       float(self.wd), self.step_count), "hlmc_net_adam_step")
+        return c["sums"]
+
+    def loss(self, sums):
+        """Host float mse_loss of a step from its device sums (synchronises; raises on a raised device status)."""
+        s = sums.cpu().tolist()
+        L.check_device("AutoencoderTrainer.step")
+        return s[0] / s[1]
+
+    def loss_tuple(self, sums, batch=None):
+        raise L.HLMCError("the autoencoder has one loss term: use AutoencoderTrainer.loss")
+
+
+def dataloader_order(n, generator=None):
+    """One epoch's row order exactly as ``iter(DataLoader(dataset_of_n_rows, shuffle=True, generator=generator))``
+    draws it (torch.utils.data: _BaseDataLoaderIter.__init__ and RandomSampler.__iter__), as an int64 CPU tensor; batch
+    k of the epoch is ``order[k * batch_size:(k + 1) * batch_size]``.  The generator is left in the state a completed
+    epoch of that DataLoader leaves it in, so consecutive calls give consecutive epochs.
+
+    generator None (the reference's loaders): two int64 ``random_()`` draws from the global generator -- the
+    iterator's base seed, discarded, then the sampler's seed -- and ``randperm(n)`` from a fresh generator seeded with
+    the second.  An explicit generator: the base seed is drawn from it and the sampler then permutes with the SAME
+    generator, and draws once more for the (empty) remainder at the end of the epoch."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be positive")
+    torch.empty((), dtype=torch.int64).random_(generator=generator)  # _base_seed
+    if generator is None:
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        return torch.randperm(n, generator=torch.Generator().manual_seed(seed))
+    order = torch.randperm(n, generator=generator)
+    torch.randperm(n, generator=generator)  # RandomSampler's remainder draw, randperm(n)[:0]
+    return order
+
+
+def fit_autoencoder(model, X, epochs=50, batch_size=32, lr=1e-3, generator=None, graph=False, warmup=2):
+    """The reference's autoencoder training (src/Conditional_VAE.py:428-452: ``DataLoader(TensorDataset(X),
+    batch_size=32, shuffle=True)``, ``Adam(lr=1e-3)``, ``mse_loss``, 50 epochs) on the device-resident X [n][d].
+    Returns the per-epoch mean batch loss (the reference's ``epoch_loss / len(loader)``) as a float64 numpy array,
+    read back once at the end; the model is left in train mode, as the reference's loop leaves it.
+
+    Step order, batch membership (``dataloader_order``) and the Adam step count are the reference loop's.  Per epoch
+    the row order is uploaded once; per step the host issues one hlmc_batch_gather into a static [batch_size][d]
+    buffer (the short last batch padded with zero rows, its row count left on the device), the Adam coefficient copy
+    and, with ``graph=True``, ONE graph replay of the whole step; ``graph=False`` issues the same kernels eagerly (the
+    same bits).  Eager is the default: measured on the MI355X at the reference's size the two modes take the same time
+    (profiles/r17/ae_timing.json).  With ``graph=True`` the first ``warmup`` steps run eagerly before the
+    capture, and a fit of no more than ``warmup`` steps runs eagerly."""
+    if not isinstance(model, SimpleAutoencoder):
+        raise TypeError("fit_autoencoder trains a SimpleAutoencoder")
+    dev = next(model.parameters()).device
+    X = L.device_matrix(X, dev)
+    n, d = X.shape
+    epochs, bs, warmup = int(epochs), int(batch_size), max(1, int(warmup))
+    if epochs < 1 or bs < 1:
+        raise ValueError("epochs and batch_size must be positive")
+    model.train()
+    lib = L.lib()
+    tr = AutoencoderTrainer(model, lr=lr)
+    xb = torch.zeros(bs, d, device=dev)
+    valid = torch.zeros(1, dtype=torch.int32, device=dev)
+    hist = torch.zeros(epochs, dtype=torch.float64, device=dev)
+    nb = (n + bs - 1) // bs
+    graph = bool(graph) and epochs * nb > warmup
+
+    def body():
+        return tr.step(xb, valid)
+
+    gs, done, fences = None, 0, []
+    tr._graph = True  # both modes stage Adam's coefficients on the device: the same kernels, replayed or not
+    try:
+        for e in range(epochs):
+            order = dataloader_order(n, generator).to(dev)
+            for k in range(nb):
+                L.check(lib.hlmc_batch_gather(L.stream(), X.data_ptr(), n, d, order.data_ptr() + 8 * k * bs,
+                                              min(bs, n - k * bs), bs, xb.data_ptr(), valid.data_ptr()),
+                        "hlmc_batch_gather")
+                if gs is not None:
+                    gs()
+                elif graph and done == warmup - 1:
+                    gs = GraphedStep(tr, body, warmup=1)  # this step eagerly, then the capture
+                else:
+                    tr.prepare_step_coefficients()
+                    body()
+                done += 1
+                if done % 256 == 0:
+                    # Adam's coefficients travel through a pinned ring of 1024 steps (prepare_step_coefficients): the
+                    # host stays less than 512 steps ahead of the device
+                    fences.append(torch.cuda.Event())
+                    fences[-1].record()
+                    if len(fences) > 1:
+                        fences.pop(0).synchronize()
+            hist[e] = tr.loss_acc[0] / nb
+            tr.loss_acc.zero_()
+        out = hist.cpu().numpy()
+        L.check_device("fit_autoencoder")
+    finally:
+        if gs is not None:
+            gs.release()
+        tr._graph = False
+        tr.release()
+    return out

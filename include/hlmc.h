@@ -32,7 +32,8 @@ enum hlmc_dtype { HLMC_F32 = 0, HLMC_BF16 = 1 };
 int hlmc_version(void);
 const char* hlmc_last_error(void);
 /* Device status word: bits a kernel raised instead of hanging or returning silently wrong values (bit 0: the one-launch
- * BatchNorm backward's grid-wide arrival count timed out, its outputs are NaN).  No synchronisation: kernels write it
+ * BatchNorm backward's grid-wide arrival count timed out, its outputs are NaN; bit 1: hlmc_batch_gather met a row index
+ * outside [0, n), that row is zeros).  No synchronisation: kernels write it
  * with system-scope stores into pinned host memory, so a launch's bit is visible once the launch has completed.  While a
  * bit is raised, hlmc_net_backward / hlmc_op_bn_bwd return HLMC_EDEVICE.  clear != 0 resets the word.  Returns the bits. */
 int hlmc_device_status(int clear);
@@ -117,11 +118,23 @@ int hlmc_zscore_apply(void* stream, const float* x, int64_t n, int64_t cols, con
  *   HybridVAE        src/Convolutional_VAE.py:75-185   (kind 0; cfg = {latent, text_dim (0 = audio-only), H, W})
  *   ConditionalVAE   src/Conditional_VAE.py:109-231    (kind 1; cfg = {latent, text_dim, num_classes, H, W})
  *   VAE (Simple)     src/Simple_VAE.py:47-105          (kind 2; cfg = {input_dim, latent, n_hidden, h_1..h_n})
+ *   SimpleAutoencoder src/Conditional_VAE.py:252-273   (kind 3; cfg = {input_dim, latent_dim}; see below)
  * and the torch train step of src/Convolutional_VAE.py:224-240.  Parameters are bound in the
  * reference's registration order (hlmc_net_param_info) as fp32 "master" tensors; dtype selects the
  * activation / MFMA operand type (HLMC_F32 exact fp32 MFMA, HLMC_BF16 bf16 MFMA with fp32 accumulate). */
 typedef struct hlmc_net hlmc_net;
-enum hlmc_net_kind { HLMC_NET_HYBRID = 0, HLMC_NET_CVAE = 1, HLMC_NET_SIMPLE = 2 };
+enum hlmc_net_kind { HLMC_NET_HYBRID = 0, HLMC_NET_CVAE = 1, HLMC_NET_SIMPLE = 2, HLMC_NET_AE = 3 };
+/* Kind 3, the deterministic autoencoder baseline: Linear(D, 1024) - ReLU - Linear(1024, 256) - ReLU - Linear(256, L)
+ * and its mirror, no BatchNorm (hlmc_net_num_bn = 0), no sampling; any input_dim, latent_dim >= 1.  Parameters:
+ * encoder.0 / 2 / 4 then decoder.0 / 2 / 4, weight then bias.  Every entry point below takes it with these rules:
+ *   hlmc_net_forward   in0 = x [B][input_dim]; recon [B][input_dim]; z (nullable) [B][latent_dim] = encoder(x);
+ *                      in1, in2, eps, dropout, recon_text, mu, logvar must be NULL.  Train mode accepts B = 1.
+ *   hlmc_net_encode    mu receives z; in1, in2 and logvar must be NULL.
+ *   hlmc_net_decode    recon = decoder(z); cond, dropout and recon_text must be NULL.
+ *   hlmc_net_backward  d_recon [B][input_dim]; d_mu (nullable) [B][latent_dim] is the upstream gradient of z, added
+ *                      to the gradient that arrives at encoder.4's output from the decoder; d_logvar and d_recon_text
+ *                      must be NULL.  One gradient bucket.
+ * A violated rule returns HLMC_EINVAL before anything is launched. */
 
 int hlmc_net_create(int kind, const int64_t* cfg, int ncfg, int dtype, hlmc_net** out);
 int hlmc_net_destroy(hlmc_net* net);
@@ -234,6 +247,35 @@ int hlmc_loss_backward(void* stream, const float* ra, const float* a, int64_t na
 int hlmc_loss_sums_backward(void* stream, const float* ra, const float* a, int64_t na, float* dra, const float* rt,
                             const float* t, int64_t nt, float* drt, const float* mu, const float* lv, int64_t nl,
                             const float* coef, float* dmu, float* dlv, double* sums3, void* ws);
+
+/* ============================================================== autoencoder train step: feed and loss
+ * The loop of src/Conditional_VAE.py:428-452 -- DataLoader(batch_size=32, shuffle=True), mse_loss, Adam -- as one
+ * captured graph replayed per step: hlmc_batch_gather, launched outside the graph with per-step arguments, fills the
+ * graph's static input buffer, and hlmc_mse_rows inside the graph reads the row count from device memory, so the short
+ * last batch of an epoch (padded with zero rows) needs no second graph.  Both allocate nothing, never synchronise and
+ * use no floating-point atomics (the same bits from run to run).
+ *
+ * hlmc_batch_gather: out [B][d] f32 = rows X[idx[b]] for b < count, zero rows for count <= b < B; valid_dev (device
+ * int32[1]) = count.  X [n][d] f32; idx: DEVICE int64 pointer to this step's count row indices; 1 <= count <= B.  An
+ * index outside [0, n) is never dereferenced: its row is written as zeros and bit 1 of the device status word
+ * (hlmc_device_status) is raised.
+ *
+ * hlmc_mse_rows: torch.nn.functional.mse_loss(recon[:valid], target[:valid]) and its gradient in one pass over the
+ * dense [B][d] f32 arrays, valid = *valid_dev clamped to [0, B], read on the device.
+ *   d_recon[b][j] = (float)(((double)recon - (double)target) * (2.0 / (valid d))) for b < valid, +0.0f for the other
+ *                   rows whatever recon holds there (NaN included);
+ *   sums2 (double[2]) = { sum over the valid rows of ((double)recon - (double)target)^2, valid d };
+ *   acc (nullable, double[1]) += sums2[0] / sums2[1] (a running loss; unchanged when valid = 0).
+ * The squared differences are added in float64 in a fixed order that depends on B and d alone: up to 16384 elements
+ * one block of 1024 threads (thread t takes the float4 units t, t + 1024, ... in order, then the xor butterfly
+ * 32, 16, .., 1 per wave and once more over the waves' totals), above that ceil(B d / 8192) <= 1024 such blocks and a
+ * second launch that adds their totals the same way.  ws: hlmc_mse_rows_workspace(B, d) bytes (0: out of range),
+ * non-decreasing in B and d. */
+int hlmc_batch_gather(void* stream, const float* X, int64_t n, int d, const int64_t* idx, int count, int B, float* out,
+                      int32_t* valid_dev);
+int64_t hlmc_mse_rows_workspace(int64_t B, int64_t d);
+int hlmc_mse_rows(void* stream, const float* recon, const float* target, int B, int d, const int32_t* valid_dev,
+                  float* d_recon, double* sums2, double* acc, void* ws);
 
 /* ============================================================== optimizer
  * torch.optim.Adam(lr, betas, eps, weight_decay) step (src/Convolutional_VAE.py:208,235) over
