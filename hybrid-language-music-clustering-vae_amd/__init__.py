@@ -22,6 +22,11 @@ Drop-in surface (reference names):
   SimpleAutoencoder, fit_autoencoder, autoencoder_kmeans_baseline, direct_kmeans_baseline
                                                (the "Autoencoder + K-Means" and "Direct Spectral" rows of
                                                 src/Conditional_VAE.py: the training loop resident on the device)
+  fit_vae, PlateauStopper, simple_vae_experiment, results.write_clustering_metrics
+                                               (the training procedure and table of src/Simple_VAE.py: DataLoader order,
+                                                Adam, ReduceLROnPlateau, early stopping and best-weights restore with
+                                                one read-back per epoch; the "VAE + KMeans" / "PCA + KMeans" rows and
+                                                the shared clustering_metrics.csv)
   pipeline.run_pipeline                        (BASELINE config[4]: 30 s clips -> mel -> scaler -> ConvVAE train ->
                                                 latents -> KMeans, resident in HBM)
 All compute runs in libhlmc.so (hand-written HIP for gfx950); see include/hlmc.h.
@@ -41,9 +46,12 @@ from . import preprocess
 from .losses import cvae_loss_function, loss_function, vae_loss
 from .models import VAE, ConditionalVAE, HybridVAE, SimpleAutoencoder
 from .optim import Adam
-from .train import AutoencoderTrainer, GraphedStep, Trainer, dataloader_order, fit_autoencoder
+from .train import (AutoencoderTrainer, GraphedStep, PlateauStopper, Trainer, VAEFitResult, dataloader_order,
+                    fit_autoencoder, fit_vae)
 from . import baselines
-from .baselines import autoencoder_kmeans_baseline, direct_kmeans_baseline
+from .baselines import autoencoder_kmeans_baseline, direct_kmeans_baseline, simple_vae_experiment
+from . import results
+from .results import write_clustering_metrics
 from . import pipeline
 
 __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_function", "vae_loss", "melspectrogram",
@@ -52,4 +60,5 @@ __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_fun
            "agglomerative_k_sweep",
            "PCA", "pca_kmeans_baseline", "TSNE",
            "Adam", "Trainer", "GraphedStep", "metrics", "SimpleAutoencoder", "AutoencoderTrainer", "dataloader_order",
-           "fit_autoencoder", "autoencoder_kmeans_baseline", "direct_kmeans_baseline"]
+           "fit_autoencoder", "autoencoder_kmeans_baseline", "direct_kmeans_baseline", "PlateauStopper", "VAEFitResult",
+           "fit_vae", "simple_vae_experiment", "write_clustering_metrics"]

@@ -151,9 +151,39 @@ int mse_blocks(int64_t B, int64_t d) {
     return (int)std::min<int64_t>((units + 2047) / 2048, kMseMaxBlocks);
 }
 
+// Step k of an epoch left sums[3 k] = sum (recon - x)^2 and sums[3 k + 2] = sum (1 + lv - mu^2 - exp lv); with its own
+// element counts na = na_nl[2 k], nl = na_nl[2 k + 1] (the short last batch differs) the reference's per-step values are
+// recon = s0 / na, kl = -0.5 s2 / nl, total = recon + beta kl.  Launched as ONE thread, which adds them in step order,
+// each operation rounded once (this file is built without FMA contraction), so a host loop over the same doubles gives
+// the same bits.
+__global__ void vae_epoch_means_kernel(const double* __restrict__ sums, const int64_t* __restrict__ na_nl, int nb,
+                                       double beta, double* __restrict__ out3) {
+    double loss = 0.0, recon = 0.0, kl = 0.0;
+    for (int k = 0; k < nb; ++k) {
+        const double r = sums[3 * k] / (double)na_nl[2 * k];
+        const double q = -0.5 * sums[3 * k + 2] / (double)na_nl[2 * k + 1];
+        loss += r + beta * q;
+        recon += r;
+        kl += q;
+    }
+    out3[0] = loss / (double)nb;
+    out3[1] = recon / (double)nb;
+    out3[2] = kl / (double)nb;
+}
+
 }  // namespace
 
 namespace ae {
+
+int vae_epoch_means(hipStream_t s, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3) {
+    HLMC_CHECK_ARG(sums && na_nl && out3, "vae_epoch_means: NULL argument");
+    HLMC_CHECK_ARG(nb >= 1, "vae_epoch_means: need nb >= 1");
+    HLMC_CHECK_ARG(beta == beta, "vae_epoch_means: beta is NaN");
+    vae_epoch_means_kernel<<<1, 1, 0, s>>>(sums, na_nl, nb, beta, out3);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
+}
+
 
 int batch_gather(hipStream_t s, const float* X, int64_t n, int d, const int64_t* idx, int count, int B, float* out,
                  int* valid_dev) {

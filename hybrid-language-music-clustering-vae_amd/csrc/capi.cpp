@@ -405,6 +405,31 @@ int hlmc_net_get_rng(const hlmc_net* h, uint64_t* seed, uint64_t* offset) {
 int hlmc_randn(void* stream, float* out, int64_t n, uint64_t seed, uint64_t offset) {
     return ops::randn(S(stream), out, n, seed, offset);
 }
+int hlmc_dropout_mask(void* stream, uint8_t* out, int64_t n, double p_drop, uint64_t seed, uint64_t offset) {
+    return ops::dropout_mask(S(stream), out, n, p_drop, seed, offset);
+}
+int hlmc_net_set_dropout_rng(hlmc_net* h, int on, uint64_t seed, uint64_t offset) {
+    HLMC_CHECK_ARG(h && offset % 4 == 0, "net is NULL / offset not a multiple of 4");
+    if (h->impl->kind != HLMC_NET_SIMPLE) {
+        set_error("hlmc_net_set_dropout_rng: only the Simple VAE has dropout layers");
+        return HLMC_EUNSUP;
+    }
+    h->impl->drop_on = on != 0;
+    h->impl->drop_seed = seed;
+    h->impl->drop_offset = offset;
+    return HLMC_OK;
+}
+int hlmc_net_get_dropout_rng(const hlmc_net* h, int* on, uint64_t* seed, uint64_t* offset) {
+    HLMC_CHECK_ARG(h && on && seed && offset, "NULL argument");
+    if (h->impl->kind != HLMC_NET_SIMPLE) {
+        set_error("hlmc_net_get_dropout_rng: only the Simple VAE has dropout layers");
+        return HLMC_EUNSUP;
+    }
+    *on = h->impl->drop_on ? 1 : 0;
+    *seed = h->impl->drop_seed;
+    *offset = h->impl->drop_offset;
+    return HLMC_OK;
+}
 int hlmc_net_set_overlap_adam(hlmc_net* h, int enable) {
     HLMC_CHECK_ARG(h, "net is NULL");
     h->impl->overlap_adam = enable != 0;
@@ -439,6 +464,9 @@ int64_t hlmc_mse_rows_workspace(int64_t B, int64_t d) { return (int64_t)ae::mse_
 int hlmc_mse_rows(void* stream, const float* recon, const float* target, int B, int d, const int32_t* valid_dev,
                   float* d_recon, double* sums2, double* acc, void* ws) {
     return ae::mse_rows(S(stream), recon, target, B, d, valid_dev, d_recon, sums2, acc, ws);
+}
+int hlmc_vae_epoch_means(void* stream, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3) {
+    return ae::vae_epoch_means(S(stream), sums, na_nl, nb, beta, out3);
 }
 
 // ------------------------------------------------------------------------------------ loss / optim

@@ -1288,11 +1288,18 @@ class SimpleNet : public NetT<T> {
     const uint8_t* mask_of(const Blk& b) const { return dropout ? dropout + b.mask_off : nullptr; }
     const uint8_t* dropout = nullptr;
     static constexpr float kKeepScale = 1.f / 0.8f;  // Dropout(0.2)
-    // train mode: the caller's mask bytes are copied into the workspace (backward reads them again)
+    static constexpr double kDropP = 0.2;
+    // train mode: the caller's mask bytes are copied into the workspace (backward reads them again); with none and
+    // the net's dropout stream on (hlmc_net_set_dropout_rng) a forward / decode draws them there in one launch and
+    // the stream advances past them (kept a multiple of 4).  An encode-only call draws nothing.
     int stage_dropout(hipStream_t s, const ForwardArgs& a) {
         dropout = nullptr;
         if (a.train && a.dropout) {
             HLMC_HIP(hipMemcpyAsync(AU8(mask_), a.dropout, (size_t)mask_total, hipMemcpyDeviceToDevice, s));
+            dropout = AU8(mask_);
+        } else if (a.train && this->drop_on && !a.encode_only) {
+            HLMC_TRY(ops::dropout_mask(s, AU8(mask_), mask_total, kDropP, this->drop_seed, this->drop_offset));
+            this->drop_offset += ((uint64_t)mask_total + 3) & ~uint64_t(3);
             dropout = AU8(mask_);
         }
         return HLMC_OK;

@@ -104,6 +104,11 @@ class NetBase {
     // reparameterisation noise drawn on the device when the caller passes no eps (ops::reparam_rng): Philox
     // stream `rng_seed`, next element rng_offset (advanced by each such forward, kept a multiple of 4)
     uint64_t rng_seed = 0, rng_offset = 0;
+    // Simple kind: the dropout keep-mask drawn on the device (ops::dropout_mask) when a train-mode forward / decode
+    // gets no mask and drop_on is set: Philox stream `drop_seed`, next element drop_offset (advanced by each such
+    // call by the mask bytes rounded up to 4).  Off by default: no mask then means no dropout.
+    bool drop_on = false;
+    uint64_t drop_seed = 0, drop_offset = 0;
     virtual int settle(hipStream_t s) = 0;  // make every gradient of the last backward final on s
 };
 

@@ -150,6 +150,9 @@ int batch_gather(hipStream_t s, const float* X, int64_t n, int d, const int64_t*
 size_t mse_rows_workspace(int64_t B, int64_t d);   // 0: arguments out of range
 int mse_rows(hipStream_t s, const float* recon, const float* target, int B, int d, const int* valid_dev, float* d_recon,
              double* sums2, double* acc, void* ws);
+// The Simple VAE's epoch means (src/Simple_VAE.py:190-196) from the per-step loss sums left on the device: one thread
+// adds the nb steps' recon / kl / total in step order in float64 and divides by nb; out3 = {loss, recon, kl}.
+int vae_epoch_means(hipStream_t s, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3);
 }  // namespace ae
 
 }  // namespace hlmc

@@ -1230,6 +1230,29 @@ __global__ void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, 
             if (4 * t + j < n) out[4 * t + j] = v[j];
     }
 }
+// Dropout keep-mask from the same stream definition: out[i] = (word of stream element offset + i) >= thresh, an integer
+// compare on the raw Philox word (no float conversion).  offset % 4 == 0, so thread t owns Philox block offset / 4 + t
+// and the bytes 4 t .. 4 t + 3: one 32-bit store where that address is 4-aligned and the group is whole, byte stores
+// otherwise (an unaligned `out`, the n % 4 tail).  thresh is 64-bit: ceil(p 2^32) reaches 2^32 for p just below 1.
+__global__ void dropout_mask_kernel(uint8_t* __restrict__ out, int64_t n, uint64_t thresh, uint64_t seed,
+                                    uint64_t offset) {
+    const int64_t groups = (n + 3) / 4;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < groups; t += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t q = offset / 4 + (uint64_t)t;
+        const uint4 w = philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u), (uint32_t)seed,
+                                      (uint32_t)(seed >> 32));
+        const uint32_t k[4] = {(uint64_t)w.x >= thresh ? 1u : 0u, (uint64_t)w.y >= thresh ? 1u : 0u,
+                               (uint64_t)w.z >= thresh ? 1u : 0u, (uint64_t)w.w >= thresh ? 1u : 0u};
+        uint8_t* p = out + 4 * t;
+        if (4 * t + 4 <= n && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(p) = k[0] | (k[1] << 8) | (k[2] << 16) | (k[3] << 24);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * t + j < n) p[j] = (uint8_t)k[j];
+        }
+    }
+}
 // z = mu + eps * exp(0.5 lv) with eps drawn here (element i of the [n_rows][L] block = stream element offset + i)
 // and stored to eps_out for the backward pass
 template <typename T>
@@ -2113,6 +2136,15 @@ int randn(hipStream_t s, float* out, int64_t n, uint64_t seed, uint64_t offset) 
     HLMC_CHECK_ARG(out && n >= 0 && offset % 4 == 0, "randn: bad arguments (offset must be a multiple of 4)");
     if (n == 0) return HLMC_OK;
     randn_kernel<<<grid_for((n + 3) / 4), kThreads, 0, s>>>(out, n, seed, offset);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
+}
+int dropout_mask(hipStream_t s, uint8_t* out, int64_t n, double p_drop, uint64_t seed, uint64_t offset) {
+    HLMC_CHECK_ARG(out && n >= 0 && offset % 4 == 0, "dropout_mask: bad arguments (offset must be a multiple of 4)");
+    HLMC_CHECK_ARG(p_drop >= 0.0 && p_drop < 1.0, "dropout_mask: p_drop must be in [0, 1)");  // false for NaN
+    if (n == 0) return HLMC_OK;
+    const uint64_t thresh = (uint64_t)std::ceil(p_drop * 4294967296.0);
+    dropout_mask_kernel<<<grid_for((n + 3) / 4), kThreads, 0, s>>>(out, n, thresh, seed, offset);
     HLMC_LAUNCHED();
     return HLMC_OK;
 }

@@ -187,6 +187,9 @@ size_t colsum_ws(int rows, int cols);
 // z = mu + eps * exp(0.5 logvar)  (z written as T with row stride ldz)
 // eps ~ N(0,1), element offset + i of the Philox4x32-10 stream `seed` (offset % 4 == 0) -> out[i]
 int randn(hipStream_t s, float* out, int64_t n, uint64_t seed, uint64_t offset);
+// Dropout keep-mask from the raw words of the same stream: out[i] = word(offset + i) >= ceil(p_drop 2^32) ? 1 : 0
+// (offset % 4 == 0, 0 <= p_drop < 1; n = 0 launches nothing)
+int dropout_mask(hipStream_t s, uint8_t* out, int64_t n, double p_drop, uint64_t seed, uint64_t offset);
 // reparam_fwd with eps drawn on the device (the same stream elements as randn) and stored to eps_out; mu_out /
 // lv_out (nullable): copies of mu / lv written by the same launch (the caller's latent outputs)
 template <typename T>

@@ -440,6 +440,36 @@ class VAE(_NativeModule):
         n = batch * sum(self.mask_widths())
         return (torch.rand(n, device=device, generator=generator) >= self.dropout_p).to(torch.uint8)
 
+    def get_dropout_rng_state(self):
+        """(on, seed, offset) of the engine's Philox dropout stream (hlmc_net_get_dropout_rng): while on, a train-mode
+        forward / decode / Trainer.step without a mask has the engine draw it in one launch (no torch.rand) and the
+        offset advances by the mask bytes rounded up to 4.  Off by default; not part of state_dict."""
+        on, seed, off = C.c_int(), C.c_uint64(), C.c_uint64()
+        L.check(L.lib().hlmc_net_get_dropout_rng(self._native_net().h, C.byref(on), C.byref(seed), C.byref(off)),
+                "hlmc_net_get_dropout_rng")
+        return bool(on.value), int(seed.value), int(off.value)
+
+    def set_dropout_rng_state(self, state):
+        on, seed, off = state
+        L.check(L.lib().hlmc_net_set_dropout_rng(self._native_net().h, int(bool(on)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                 int(off) & 0xFFFFFFFFFFFFFFFF), "hlmc_net_set_dropout_rng")
+
+    def _mask_for(self, batch, device, dropout_mask):
+        """The mask a train-mode call hands the engine: the caller's; else None while the engine's own dropout stream
+        is on (it draws the mask itself) and no graph is being captured; else one drawn with torch (make_dropout_mask)."""
+        if not self.training or dropout_mask is not None:
+            return dropout_mask
+        on = C.c_int(0)
+        if self._net is not None:  # no native net yet: the stream is in its initial state, off
+            seed, off = C.c_uint64(), C.c_uint64()
+            L.check(L.lib().hlmc_net_get_dropout_rng(self._net.h, C.byref(on), C.byref(seed), C.byref(off)),
+                    "hlmc_net_get_dropout_rng")
+        # under torch.cuda.graph capture the stream's host-side offset would freeze into the graph (every replay the
+        # same mask), as eps's would (_run): torch's graph-safe generator then
+        if on.value and not (torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            return None
+        return self.make_dropout_mask(batch, device)
+
     def encode(self, x):
         return self._encode_native(x.float().contiguous())
 
@@ -447,14 +477,11 @@ class VAE(_NativeModule):
         """self.decoder(z) — src/Simple_VAE.py:95-96.  In train mode the decoder's Dropout(0.2) layers apply
         `dropout_mask` (the forward's keep-mask layout, make_dropout_mask; drawn when None).  Inference entry:
         no autograd graph is recorded."""
-        if self.training and dropout_mask is None:
-            dropout_mask = self.make_dropout_mask(z.shape[0], z.device)
-        return self._decode_native(z, None, dropout_mask if self.training else None)["recon"]
+        return self._decode_native(z, None, self._mask_for(z.shape[0], z.device, dropout_mask))["recon"]
 
     def forward(self, x, eps=None, dropout_mask=None):
         B = x.shape[0]
-        if self.training and dropout_mask is None:
-            dropout_mask = self.make_dropout_mask(B, x.device)
+        dropout_mask = self._mask_for(B, x.device, dropout_mask)
         recon, _, mu, lv, z = self._run(x.float().contiguous(), None, None, None if eps is None else eps.contiguous(),
                                         dropout_mask if self.training else None)
         return recon, mu, lv, z

@@ -96,6 +96,7 @@ class Trainer:
         # weights change only through hlmc_net_adam_step (which refreshes the packed GEMM layouts)
         L.check(L.lib().hlmc_net_set_trust_packs(self.net.h, 1))
         self._cache = {}
+        self._engine_dropout = None  # None: ask the engine each step (_dropout_stream_on)
 
     def _buffers(self, B):
         if B not in self._cache:
@@ -132,11 +133,14 @@ class Trainer:
         seed, off = sd["rng"]
         self.model.set_rng_state((keyed_seed(int(seed), self._rng_key), int(off)))
 
-    def step(self, in0, in1=None, in2=None, eps=None, dropout=None, before_adam=None):
+    def step(self, in0, in1=None, in2=None, eps=None, dropout=None, before_adam=None, sums=None):
         """One optimisation step on a batch; returns device float64 sums (sum sq audio err, sum sq text err,
         sum(1+lv-mu^2-e^lv)) from which the reference's loss tuple follows.  before_adam (optional callable)
         is invoked once the backward pass is enqueued, before the optimizer update (the inputs are no longer
-        read from there on: a caller may start refilling them on another stream)."""
+        read from there on: a caller may start refilling them on another stream).  sums (optional): a contiguous
+        device float64[3] destination for those sums instead of the Trainer's own buffer (fit_vae: a row of its
+        per-epoch table), returned in its place.  Simple VAE, dropout None: the mask is drawn by the engine when the
+        net's dropout stream is on (VAE.set_dropout_rng_state), else by VAE.make_dropout_mask."""
         lib = L.lib()
         s = L.stream()
         B = in0.shape[0]
@@ -144,11 +148,18 @@ class Trainer:
             self._check_bn_flat()
         c = self._buffers(B)
         out, d = c["out"], c["d"]
+        if sums is None:
+            sums = c["sums"]
+        elif (sums.dtype != torch.float64 or sums.numel() != 3 or not sums.is_contiguous()
+              or sums.device != c["sums"].device):
+            raise ValueError("sums must be a contiguous float64 tensor of 3 elements on the model's device")
         # eps None: the engine draws the reparameterisation noise on the device (Philox, hlmc_net_set_rng) — except
         # under graph capture, where the host-side stream offset would freeze into the graph: torch's graph-safe randn
         if eps is None and self._graph:
             eps = torch.randn(B, self.model.latent_dim, device=self.device)
-        if self.kind == "simple" and dropout is None:
+        # Simple VAE without a mask: the engine draws it while its dropout stream is on -- except in graph mode, where
+        # the stream's host-side offset would freeze into the graph like eps's: torch's graph-safe rand instead
+        if self.kind == "simple" and dropout is None and (self._graph or not self._dropout_stream_on()):
             dropout = self.model.make_dropout_mask(B, self.device)
         L.check(lib.hlmc_net_forward(self.net.h, s, B, 1, L.ptr(in0), L.ptr(in1), L.ptr(in2), L.ptr(eps),
                                      L.ptr(dropout), L.ptr(out["recon"]), L.ptr(out.get("recon_text")),
@@ -163,7 +174,7 @@ class Trainer:
         L.check(lib.hlmc_loss_sums_backward(s, L.ptr(out["recon"]), L.ptr(in0), na, L.ptr(d["recon"]), L.ptr(rt),
                                             L.ptr(t), nt, L.ptr(d.get("recon_text")), L.ptr(out["mu"]),
                                             L.ptr(out["logvar"]), nl, c["coef"].data_ptr(), L.ptr(d["mu"]),
-                                            L.ptr(d["logvar"]), c["sums"].data_ptr(), c["lws"].data_ptr()),
+                                            L.ptr(d["logvar"]), sums.data_ptr(), c["lws"].data_ptr()),
                 "hlmc_loss_sums_backward")
         L.check(lib.hlmc_net_backward(self.net.h, s, B, L.ptr(d["recon"]), L.ptr(d.get("recon_text")), L.ptr(d["mu"]),
                                       L.ptr(d["logvar"]), c["ws"].data_ptr()), "hlmc_net_backward")
@@ -180,12 +191,22 @@ class Trainer:
         if self._graph:  # coefficients staged by prepare_step_coefficients()
             L.check(lib.hlmc_net_adam_step_dev(self.net.h, s, *self._mv, self._coef_dev.data_ptr()),
                     "hlmc_net_adam_step_dev")
-            return c["sums"]
+            return sums
         self.step_count += 1
         b1, b2 = self.betas
         L.check(lib.hlmc_net_adam_step(self.net.h, s, *self._mv, float(self.lr), float(b1), float(b2), float(self.eps),
                                        float(self.wd), self.step_count), "hlmc_net_adam_step")
-        return c["sums"]
+        return sums
+
+    def _dropout_stream_on(self):
+        """Whether the engine draws the Simple VAE's dropout masks itself (hlmc_net_set_dropout_rng).  A caller that
+        switched the stream itself sets ``_engine_dropout`` (fit_vae) and spares the step the query."""
+        if self._engine_dropout is not None:
+            return self._engine_dropout
+        on, seed, off = L.c_int(), L.C.c_uint64(), L.C.c_uint64()
+        L.check(L.lib().hlmc_net_get_dropout_rng(self.net.h, L.C.byref(on), L.C.byref(seed), L.C.byref(off)),
+                "hlmc_net_get_dropout_rng")
+        return bool(on.value)
 
     def prepare_step_coefficients(self):
         """Advance the step counter and stage that step's Adam coefficients (host -> pinned ring -> device,
@@ -531,3 +552,168 @@ def fit_autoencoder(model, X, epochs=50, batch_size=32, lr=1e-3, generator=None,
         tr._graph = False
         tr.release()
     return out
+
+
+# ----------------------------------------------------------------------------------------- Simple VAE fit
+class PlateauStopper:
+    """The two plateau rules of the reference's Simple VAE loop (src/Simple_VAE.py:151-153, 202-217) as one host-side
+    state machine; ``update(loss) -> (improved, lr, stop)`` once per epoch with the epoch's mean batch loss.
+
+    ``lr`` follows ``torch.optim.lr_scheduler.ReduceLROnPlateau(mode='min', factor, patience=lr_patience, threshold,
+    threshold_mode='rel', cooldown=0, min_lr, eps)`` exactly: an epoch is good iff ``loss < best * (1 - threshold)``;
+    after more than ``lr_patience`` bad epochs in a row the rate becomes ``max(lr * factor, min_lr)`` -- if that lowers
+    it by more than ``eps`` -- and the count starts again.  ``improved`` / ``stop`` follow the reference's own counter:
+    improved iff ``loss < best_loss`` (strict, no threshold; the moment it saves best_vae_model.pth), stop once
+    ``stop_patience`` epochs in a row have not improved.  The rules differ on purpose: the scheduler ignores improvements
+    under 1e-4 relative, the stopper does not.  A NaN loss is a bad epoch for both."""
+
+    def __init__(self, lr, factor=0.5, lr_patience=15, stop_patience=15, threshold=1e-4, min_lr=0.0, eps=1e-8):
+        if factor >= 1.0:
+            raise ValueError("Factor should be < 1.0.")
+        self.lr, self.factor, self.lr_patience, self.stop_patience = float(lr), float(factor), lr_patience, stop_patience
+        self.threshold, self.min_lr, self.eps = float(threshold), float(min_lr), float(eps)
+        self.sched_best, self.num_bad_epochs = float("inf"), 0
+        self.best_loss, self.patience_counter = float("inf"), 0
+        self.epoch, self.best_epoch = -1, None
+
+    def update(self, loss):
+        loss = float(loss)
+        self.epoch += 1
+        if loss < self.sched_best * (1.0 - self.threshold):
+            self.sched_best, self.num_bad_epochs = loss, 0
+        else:
+            self.num_bad_epochs += 1
+        if self.num_bad_epochs > self.lr_patience:
+            new_lr = max(self.lr * self.factor, self.min_lr)
+            if self.lr - new_lr > self.eps:
+                self.lr = new_lr
+            self.num_bad_epochs = 0
+        improved = loss < self.best_loss
+        if improved:
+            self.best_loss, self.patience_counter, self.best_epoch = loss, 0, self.epoch
+        else:
+            self.patience_counter += 1
+        return improved, self.lr, self.patience_counter >= self.stop_patience
+
+
+_DROPOUT_STREAM_KEY = 0xD1B54A32D192ED03  # the dropout stream's seed = the eps stream's seed + this (mod 2^64)
+
+
+class VAEFitResult:
+    """What ``fit_vae`` returns.  history: dict of float64 numpy arrays ``loss``, ``recon``, ``kl`` (the epoch's mean
+    batch values, src/Simple_VAE.py:194-196) and ``lr`` (the rate the epoch's steps ran with), one entry per epoch run;
+    best_epoch / best_loss: the last strict improvement (0-based; None / inf if no epoch's loss was a number);
+    stopped_epoch: the epoch early stopping broke after (None: all epochs ran); best_state: the weights and BatchNorm
+    buffers at best_epoch as a state_dict of device tensors (``torch.save(result.best_state, 'best_vae_model.pth')`` writes
+    the reference's file); eps_rng / dropout_rng: the final (seed, offset) of the engine's two Philox streams."""
+
+    def __init__(self, history, best_epoch, best_loss, stopped_epoch, best_state, eps_rng, dropout_rng):
+        self.history, self.best_epoch, self.best_loss, self.stopped_epoch = history, best_epoch, best_loss, stopped_epoch
+        self.best_state, self.eps_rng, self.dropout_rng = best_state, eps_rng, dropout_rng
+
+    def __repr__(self):
+        return (f"VAEFitResult(epochs={len(self.history['loss'])}, best_epoch={self.best_epoch}, "
+                f"best_loss={self.best_loss:.6g}, stopped_epoch={self.stopped_epoch})")
+
+
+def fit_vae(model, X, epochs=500, batch_size=32, lr=1e-4, beta=0.8, patience=15, lr_factor=0.5, lr_patience=15,
+            generator=None, dropout_seed=None, restore_best=True):
+    """The reference's Simple VAE training (src/Simple_VAE.py:131-226) on the device-resident X [n][d]:
+    ``DataLoader(batch_size=32, shuffle=True)``, ``Adam(1e-4)``, ``vae_loss(beta=0.8)``, ``ReduceLROnPlateau(mode='min',
+    factor=0.5, patience=15)`` stepped on the epoch's mean batch loss, early stopping after ``patience`` epochs without
+    a strictly lower loss, the best weights kept at every improvement and put back at the end (``restore_best``).
+    Returns a ``VAEFitResult``; the model is left in train mode, as the reference's loop leaves it.
+
+    Per epoch the row order (``dataloader_order``) is uploaded once.  Per step: one hlmc_batch_gather into a
+    [batch_size][d] buffer -- the last n % batch_size rows into a buffer of their own, run as a real smaller batch, so
+    BatchNorm's statistics cover exactly those rows -- and one ``Trainer.step`` whose noise comes from the engine's two
+    Philox streams (eps: hlmc_net_set_rng; dropout masks: hlmc_net_set_dropout_rng, switched on for the fit) and whose
+    loss sums land in the step's row of a per-epoch device table.  At the epoch's end one hlmc_vae_epoch_means launch
+    and ONE read-back of three doubles -- the only synchronisation of the epoch, needed for the plateau decision --
+    feed ``PlateauStopper``; on an improvement every parameter and BatchNorm buffer (num_batches_tracked included) goes
+    into a preallocated snapshot with one ``torch._foreach_copy_``.
+
+    The epoch means add the float64 loss of every step; the reference adds their float32 ``.item()`` values, about
+    1e-7 relative apart, which can matter only at an exact tie of the ``<`` comparisons.  ``dropout_seed`` None: the
+    dropout stream's seed is derived from the model's eps seed (itself ``torch.initial_seed()`` when the model was
+    built), so one ``torch.manual_seed`` fixes the run; a model fitted again with the same seed continues the stream.
+    A last batch of one row (``n % batch_size == 1``) raises ValueError before anything is launched, as torch's
+    train-mode BatchNorm does at that batch.
+
+    The reference's own batch order after epoch 1 is not reproducible by anyone: on the CPU its dropout and
+    ``randn_like`` draw from the same global generator the DataLoader seeds itself from, so the order depends on how
+    many numbers those layers consumed.  Here the global generator (or ``generator``) is consumed by
+    ``dataloader_order`` alone."""
+    if not isinstance(model, VAE):
+        raise TypeError("fit_vae trains a models.VAE (the Simple VAE)")
+    dev = next(model.parameters()).device
+    X = L.device_matrix(X, dev)
+    n, d = X.shape
+    epochs, bs = int(epochs), int(batch_size)
+    if epochs < 1 or bs < 1:
+        raise ValueError("epochs and batch_size must be positive")
+    if d != model.input_dim:
+        raise ValueError(f"X must have {model.input_dim} columns, got {d}")
+    if int(patience) < 1 or int(lr_patience) < 0:
+        raise ValueError("patience must be >= 1 and lr_patience >= 0")
+    nfull, tail = divmod(n, bs)
+    if bs == 1 or tail == 1:
+        raise ValueError(f"a batch of one row (n = {n}, batch_size = {bs}): BatchNorm in train mode needs more than "
+                         f"1 value per channel")
+    stopper = PlateauStopper(lr, factor=lr_factor, lr_patience=int(lr_patience), stop_patience=int(patience))
+    model.train()
+    lib = L.lib()
+    tr = Trainer(model, lr=lr, beta=beta)
+    eps_seed, _ = model.get_rng_state()
+    if dropout_seed is None:
+        dropout_seed = keyed_seed(eps_seed, _DROPOUT_STREAM_KEY)
+    dropout_seed = int(dropout_seed) & 0xFFFFFFFFFFFFFFFF
+    _, old_seed, old_off = model.get_dropout_rng_state()
+    nb, latent = nfull + (1 if tail else 0), model.latent_dim
+    xb = torch.empty(bs, d, device=dev) if nfull else None
+    xt = torch.empty(tail, d, device=dev) if tail else None
+    valid = torch.zeros(1, dtype=torch.int32, device=dev)
+    sums = torch.zeros(nb, 3, dtype=torch.float64, device=dev)
+    rows = [bs] * nfull + ([tail] if tail else [])
+    na_nl = torch.tensor([[r * d, r * latent] for r in rows], dtype=torch.int64).to(dev)
+    out3 = torch.zeros(3, dtype=torch.float64, device=dev)
+    sd = model.state_dict()  # detached views of the live parameters and buffers, in the file's key order
+    live = list(sd.values())
+    snap = [torch.empty_like(t) for t in live]
+    hist = {k: [] for k in ("loss", "recon", "kl", "lr")}
+    stopped = None
+    try:
+        model.set_dropout_rng_state((True, dropout_seed, old_off if old_seed == dropout_seed else 0))
+        tr._engine_dropout = True
+        for e in range(epochs):
+            order = dataloader_order(n, generator).to(dev)
+            for k, r in enumerate(rows):
+                buf = xb if r == bs else xt
+                L.check(lib.hlmc_batch_gather(L.stream(), X.data_ptr(), n, d, order.data_ptr() + 8 * k * bs, r, r,
+                                              buf.data_ptr(), valid.data_ptr()), "hlmc_batch_gather")
+                tr.step(buf, sums=sums[k])
+            L.check(lib.hlmc_vae_epoch_means(L.stream(), sums.data_ptr(), na_nl.data_ptr(), nb, float(tr.beta),
+                                             out3.data_ptr()), "hlmc_vae_epoch_means")
+            loss, recon, kl = out3.cpu().tolist()  # the epoch's one synchronisation
+            L.check_device("fit_vae")
+            for key, v in zip(("loss", "recon", "kl", "lr"), (loss, recon, kl, float(tr.lr))):
+                hist[key].append(v)
+            improved, tr.lr, stop = stopper.update(loss)
+            if improved:
+                torch._foreach_copy_(snap, live)
+            if stop:
+                stopped = e
+                break
+    finally:
+        # release first: the engine trusts the packed weights Adam wrote, so weights restored behind it would go unseen
+        tr.release()
+        try:
+            if restore_best and stopper.best_epoch is not None:
+                torch._foreach_copy_(live, snap)
+        finally:
+            _, seed_now, off_now = model.get_dropout_rng_state()
+            model.set_dropout_rng_state((False, seed_now, off_now))
+    best_state = type(sd)(zip(sd.keys(), snap)) if stopper.best_epoch is not None else None
+    return VAEFitResult({k: np.asarray(v, dtype=np.float64) for k, v in hist.items()}, stopper.best_epoch,
+                        stopper.best_loss, stopped, best_state, model.get_rng_state(),
+                        model.get_dropout_rng_state()[1:])

@@ -169,6 +169,32 @@ int hlmc_net_forward(hlmc_net* net, void* stream, int64_t batch, int train, cons
 int hlmc_net_set_rng(hlmc_net* net, uint64_t seed, uint64_t offset);
 int hlmc_net_get_rng(const hlmc_net* net, uint64_t* seed, uint64_t* offset);
 int hlmc_randn(void* stream, float* out, int64_t n, uint64_t seed, uint64_t offset);
+/* Device dropout stream (replaces the nn.Dropout(0.2) draws of src/Simple_VAE.py:57-61; as with eps, the values are
+ * not a parity contract, any Bernoulli(0.8) stream serves).
+ *
+ * hlmc_dropout_mask: out[i] (uint8) = 1 (keep) or 0 for i in [0, n), decided by element g = offset + i of the
+ * Philox4x32-10 stream `seed` hlmc_randn defines: the raw 32-bit word, component g % 4 of the block at counter
+ * {g / 4 as 64 bits, 0, 0}, key {seed low, seed high}.  Keep iff word >= T, T = ceil(p_drop * 2^32) computed on the
+ * host in double (858993460 for 0.2; 0 for p_drop = 0: every element kept).  An integer compare: no float conversion,
+ * so a host restatement is exact.  One thread per Philox block writes its four bytes as one 32-bit store where
+ * out + i is 4-aligned and as bytes otherwise (an unaligned out, the n % 4 tail); nothing outside [out, out + n) is
+ * written.  No atomics, no scratch, the same bytes from run to run.  Checked on the host before any launch: out
+ * non-NULL, n >= 0 (0 launches nothing), offset % 4 == 0, 0 <= p_drop < 1; else HLMC_EINVAL.
+ *
+ * hlmc_net_set_dropout_rng / hlmc_net_get_dropout_rng (Simple kind only, HLMC_EUNSUP otherwise; offset % 4 == 0): a
+ * net's dropout stream, off when the net is created.  While off nothing changes: dropout == NULL in train mode means no
+ * dropout.  While on, a train-mode hlmc_net_forward or hlmc_net_decode with dropout == NULL fills the workspace's mask
+ * (batch * sum of the 2 n hidden widths bytes: the encoder blocks' [batch][width] masks, then the decoder blocks')
+ * with one hlmc_dropout_mask launch at p_drop = 0.2 from the net's offset, and advances the offset by that byte count
+ * rounded up to a multiple of 4; hlmc_net_backward reads the mask from the workspace as for a caller's mask.  An explicit
+ * mask is used as before and does not advance the stream; eval mode and hlmc_net_encode draw nothing.  A train-mode
+ * hlmc_net_encode therefore runs its encoder blocks WITHOUT dropout even while the stream is on (it takes no mask
+ * argument either), unlike the encoder half of a train-mode hlmc_net_forward.  The offset is host-side state passed to
+ * the launch by value: a call recorded into a HIP graph would replay one fixed mask, so callers that capture a step pass
+ * an explicit mask (train.py and models.py do). */
+int hlmc_dropout_mask(void* stream, uint8_t* out, int64_t n, double p_drop, uint64_t seed, uint64_t offset);
+int hlmc_net_set_dropout_rng(hlmc_net* net, int on, uint64_t seed, uint64_t offset);
+int hlmc_net_get_dropout_rng(const hlmc_net* net, int* on, uint64_t* seed, uint64_t* offset);
 /* encoder only (latent extraction, src/Convolutional_VAE.py:286-303): mu, logvar */
 int hlmc_net_encode(hlmc_net* net, void* stream, int64_t batch, int train, const float* in0, const float* in1,
                     const float* in2, float* mu, float* logvar, void* ws);
@@ -276,6 +302,17 @@ int hlmc_batch_gather(void* stream, const float* X, int64_t n, int d, const int6
 int64_t hlmc_mse_rows_workspace(int64_t B, int64_t d);
 int hlmc_mse_rows(void* stream, const float* recon, const float* target, int B, int d, const int32_t* valid_dev,
                   float* d_recon, double* sums2, double* acc, void* ws);
+
+/* ============================================================== Simple VAE fit: epoch losses
+ * The epoch means of src/Simple_VAE.py:190-196 without a read-back per step.  Step k of the epoch wrote its loss sums
+ * (hlmc_loss_sums_backward) to sums[k] (DEVICE double[nb][3]); na_nl (DEVICE int64[nb][2]) holds each step's element
+ * counts {batch * input_dim, batch * latent} (the short last batch has its own).  One launch, one thread, float64, in
+ * step order, every operation rounded once (no FMA contraction):
+ *   recon_k = sums[k][0] / na_k,  kl_k = -0.5 * sums[k][2] / nl_k,  total_k = recon_k + beta * kl_k,
+ *   out3 (DEVICE double[3]) = { sum total_k / nb, sum recon_k / nb, sum kl_k / nb }.
+ * The reference adds the float32 .item() of each step's loss; these are the float64 values of the same steps, about
+ * 1e-7 relative apart.  Host checks: pointers non-NULL, nb >= 1, beta not NaN; else HLMC_EINVAL before any launch. */
+int hlmc_vae_epoch_means(void* stream, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3);
 
 /* ============================================================== optimizer
  * torch.optim.Adam(lr, betas, eps, weight_decay) step (src/Convolutional_VAE.py:208,235) over
