@@ -27,6 +27,12 @@ Drop-in surface (reference names):
                                                 Adam, ReduceLROnPlateau, early stopping and best-weights restore with
                                                 one read-back per epoch; the "VAE + KMeans" / "PCA + KMeans" rows and
                                                 the shared clustering_metrics.csv)
+  fit_conv_vae, extract_latents, random_split_indices, convolutional_vae_experiment, conditional_vae_experiment
+                                               (the training runs and tables of src/Convolutional_VAE.py and
+                                                src/Conditional_VAE.py: random_split, shuffled training and unshuffled
+                                                validation passes resident on the device, early stopping on the
+                                                validation loss with one read-back per epoch; the 'Convolutional VAE'
+                                                and 'Conditional VAE' rows)
   pipeline.run_pipeline                        (BASELINE config[4]: 30 s clips -> mel -> scaler -> ConvVAE train ->
                                                 latents -> KMeans, resident in HBM)
 All compute runs in libhlmc.so (hand-written HIP for gfx950); see include/hlmc.h.
@@ -46,10 +52,11 @@ from . import preprocess
 from .losses import cvae_loss_function, loss_function, vae_loss
 from .models import VAE, ConditionalVAE, HybridVAE, SimpleAutoencoder
 from .optim import Adam
-from .train import (AutoencoderTrainer, GraphedStep, PlateauStopper, Trainer, VAEFitResult, dataloader_order,
-                    fit_autoencoder, fit_vae)
+from .train import (AutoencoderTrainer, ConvFitResult, GraphedStep, PlateauStopper, Trainer, VAEFitResult,
+                    dataloader_order, extract_latents, fit_autoencoder, fit_conv_vae, fit_vae, random_split_indices)
 from . import baselines
-from .baselines import autoencoder_kmeans_baseline, direct_kmeans_baseline, simple_vae_experiment
+from .baselines import (autoencoder_kmeans_baseline, conditional_vae_experiment, convolutional_vae_experiment,
+                        direct_kmeans_baseline, simple_vae_experiment)
 from . import results
 from .results import write_clustering_metrics
 from . import pipeline
@@ -61,4 +68,5 @@ __all__ = ["HybridVAE", "ConditionalVAE", "VAE", "loss_function", "cvae_loss_fun
            "PCA", "pca_kmeans_baseline", "TSNE",
            "Adam", "Trainer", "GraphedStep", "metrics", "SimpleAutoencoder", "AutoencoderTrainer", "dataloader_order",
            "fit_autoencoder", "autoencoder_kmeans_baseline", "direct_kmeans_baseline", "PlateauStopper", "VAEFitResult",
-           "fit_vae", "simple_vae_experiment", "write_clustering_metrics"]
+           "fit_vae", "simple_vae_experiment", "write_clustering_metrics", "random_split_indices", "ConvFitResult",
+           "fit_conv_vae", "extract_latents", "convolutional_vae_experiment", "conditional_vae_experiment"]

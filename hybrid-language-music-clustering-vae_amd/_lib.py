@@ -73,6 +73,7 @@ _SIGS = {
     "hlmc_net_set_dropout_rng": (c_int, [c_vp, c_int, C.c_uint64, C.c_uint64]),
     "hlmc_net_get_dropout_rng": (c_int, [c_vp, C.POINTER(c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hlmc_vae_epoch_means": (c_int, [c_vp, c_vp, c_vp, c_int, c_f64, c_vp]),
+    "hlmc_fit_epoch_totals": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_f64, c_f64, c_f64, c_f64, c_vp]),
     "hlmc_net_settle": (c_int, [c_vp, c_vp]),
     "hlmc_net_grad_buckets": (c_int, [c_vp, C.POINTER(c_int), c_int]),
     "hlmc_net_set_bucket_sync": (c_int, [c_vp, c_int]),

@@ -171,9 +171,52 @@ __global__ void vae_epoch_means_kernel(const double* __restrict__ sums, const in
     out3[2] = kl / (double)nb;
 }
 
+// An epoch of a convolutional VAE fit left one row of loss sums per training step and one per validation batch
+// (s[0] = sum (ra - a)^2, s[1] = sum (rt - t)^2, s[2] = sum (1 + lv - mu^2 - exp lv)).  Per row kld = -0.5 s[2] and
+// total = (s[0] + text_weight s[1]) + beta kld, in that association.  ONE thread adds the rows in step order, each
+// operation rounded once (no FMA contraction in this file), so a host loop over the same doubles gives the same bits.
+__global__ void fit_epoch_totals_kernel(const double* __restrict__ train_sums, int nt,
+                                        const double* __restrict__ val_sums, int nv, double text_weight, double beta,
+                                        double train_div, double val_div, double* __restrict__ out5) {
+    double total = 0.0, audio = 0.0, text = 0.0, kld = 0.0, val = 0.0;
+    for (int k = 0; k < nt; ++k) {
+        const double* s = train_sums + 3 * k;
+        const double q = -0.5 * s[2];
+        const double tw = text_weight * s[1];
+        const double bq = beta * q;
+        total += (s[0] + tw) + bq;
+        audio += s[0];
+        text += s[1];
+        kld += q;
+    }
+    for (int k = 0; k < nv; ++k) {
+        const double* s = val_sums + 3 * k;
+        const double q = -0.5 * s[2];
+        const double tw = text_weight * s[1];
+        const double bq = beta * q;
+        val += (s[0] + tw) + bq;
+    }
+    out5[0] = total / train_div;
+    out5[1] = audio / train_div;
+    out5[2] = text / train_div;
+    out5[3] = kld / train_div;
+    out5[4] = val / val_div;
+}
+
 }  // namespace
 
 namespace ae {
+
+int fit_epoch_totals(hipStream_t s, const double* train_sums, int nt, const double* val_sums, int nv,
+                     double text_weight, double beta, double train_div, double val_div, double* out5) {
+    HLMC_CHECK_ARG(train_sums && val_sums && out5, "fit_epoch_totals: NULL argument");
+    HLMC_CHECK_ARG(nt >= 1 && nv >= 1, "fit_epoch_totals: need nt >= 1 and nv >= 1");
+    HLMC_CHECK_ARG(text_weight == text_weight && beta == beta, "fit_epoch_totals: text_weight or beta is NaN");
+    HLMC_CHECK_ARG(train_div > 0.0 && val_div > 0.0, "fit_epoch_totals: need train_div > 0 and val_div > 0");
+    fit_epoch_totals_kernel<<<1, 1, 0, s>>>(train_sums, nt, val_sums, nv, text_weight, beta, train_div, val_div, out5);
+    HLMC_LAUNCHED();
+    return HLMC_OK;
+}
 
 int vae_epoch_means(hipStream_t s, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3) {
     HLMC_CHECK_ARG(sums && na_nl && out3, "vae_epoch_means: NULL argument");

@@ -468,6 +468,10 @@ int hlmc_mse_rows(void* stream, const float* recon, const float* target, int B, 
 int hlmc_vae_epoch_means(void* stream, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3) {
     return ae::vae_epoch_means(S(stream), sums, na_nl, nb, beta, out3);
 }
+int hlmc_fit_epoch_totals(void* stream, const double* train_sums, int nt, const double* val_sums, int nv,
+                          double text_weight, double beta, double train_div, double val_div, double* out5) {
+    return ae::fit_epoch_totals(S(stream), train_sums, nt, val_sums, nv, text_weight, beta, train_div, val_div, out5);
+}
 
 // ------------------------------------------------------------------------------------ loss / optim
 int64_t hlmc_loss_workspace(int64_t na, int64_t nt, int64_t nl) { return (int64_t)ops::vae_sums_ws(na, nt, nl); }

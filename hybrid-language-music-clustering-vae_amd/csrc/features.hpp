@@ -153,6 +153,11 @@ int mse_rows(hipStream_t s, const float* recon, const float* target, int B, int 
 // The Simple VAE's epoch means (src/Simple_VAE.py:190-196) from the per-step loss sums left on the device: one thread
 // adds the nb steps' recon / kl / total in step order in float64 and divides by nb; out3 = {loss, recon, kl}.
 int vae_epoch_means(hipStream_t s, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3);
+// The convolutional VAEs' epoch totals (src/Convolutional_VAE.py:237-256, src/Conditional_VAE.py:331-345) from the loss
+// sums of the epoch's nt training steps and nv validation batches: one thread, float64, step order;
+// out5 = {train total, audio, text, kld} / train_div and {validation total} / val_div.
+int fit_epoch_totals(hipStream_t s, const double* train_sums, int nt, const double* val_sums, int nv,
+                     double text_weight, double beta, double train_div, double val_div, double* out5);
 }  // namespace ae
 
 }  // namespace hlmc

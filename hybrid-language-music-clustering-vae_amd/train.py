@@ -717,3 +717,261 @@ def fit_vae(model, X, epochs=500, batch_size=32, lr=1e-4, beta=0.8, patience=15,
     return VAEFitResult({k: np.asarray(v, dtype=np.float64) for k, v in hist.items()}, stopper.best_epoch,
                         stopper.best_loss, stopped, best_state, model.get_rng_state(),
                         model.get_dropout_rng_state()[1:])
+
+
+# ----------------------------------------------------------------------------------------- convolutional VAE fits
+def random_split_indices(n, lengths, generator=None):
+    """The index tensors of ``torch.utils.data.random_split(range(n), lengths, generator)`` (int64, CPU): one
+    ``torch.randperm(n, generator=generator)`` on the host cut into consecutive slices; ``generator`` None consumes
+    the global generator exactly as torch does.  Only integer lengths that sum to n are accepted (torch's fractional
+    lengths are not)."""
+    n = int(n)
+    lengths = list(lengths)
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 for v in lengths):
+        raise ValueError(f"lengths must be non-negative integers, got {lengths}")
+    if n < 0 or sum(int(v) for v in lengths) != n:
+        raise ValueError("Sum of input lengths does not equal the length of the input dataset!")
+    perm = torch.randperm(n, generator=generator)
+    return list(torch.split(perm, [int(v) for v in lengths]))
+
+
+def split_sizes(n, val_fraction=0.15):
+    """(train_size, val_size) of the two scripts' split: ``int((1 - val_fraction) * n)`` -- for 0.15 the reference's
+    ``int(0.85 * len(dataset))`` -- and the rest."""
+    train = int((1 - val_fraction) * int(n))
+    return train, int(n) - train
+
+
+class ConvFitResult:
+    """What ``fit_conv_vae`` returns.  history: dict of float64 numpy arrays ``train_loss``, ``audio``, ``text``, ``kld``
+    and ``val_loss``, one entry per epoch run (the epoch's sums over the training steps, and over the validation
+    batches, divided as the script divides them); best_epoch / best_val_loss: the last strict improvement of the
+    validation loss (0-based; None / inf if no epoch's was a number); stopped_epoch: the epoch early stopping broke
+    after (None: all epochs ran); best_state: the weights and BatchNorm buffers at best_epoch as a state_dict of device
+    tensors; train_idx / val_idx: the split (int64, CPU); eps_rng: the final (seed, offset) of the engine's Philox
+    stream."""
+
+    def __init__(self, history, best_epoch, best_val_loss, stopped_epoch, best_state, train_idx, val_idx, eps_rng):
+        self.history, self.best_epoch, self.best_val_loss = history, best_epoch, best_val_loss
+        self.stopped_epoch, self.best_state = stopped_epoch, best_state
+        self.train_idx, self.val_idx, self.eps_rng = train_idx, val_idx, eps_rng
+
+    def __repr__(self):
+        return (f"ConvFitResult(epochs={len(self.history['val_loss'])}, best_epoch={self.best_epoch}, "
+                f"best_val_loss={self.best_val_loss:.6g}, stopped_epoch={self.stopped_epoch})")
+
+
+_CONV_DEFAULTS = {"hybrid": dict(beta=1.0, text_weight=350.0, patience=15, normalize="samples"),
+                  "cvae": dict(beta=4.0, text_weight=200.0, patience=20, normalize="batches")}
+
+
+def _conv_inputs(model, audio, text, cond, finite):
+    """The input tensors a HybridVAE / ConditionalVAE takes, checked where they live (no engine call; the finite test
+    of a device tensor is a torch reduction on that device): ``(kind, [audio, text, cond] as float32 [n][row] matrices, None where the model takes none)``."""
+    if isinstance(model, ConditionalVAE):
+        kind = "cvae"
+        if text is None or cond is None:
+            raise ValueError("a ConditionalVAE needs text and cond")
+        widths = (model.text_dim, model.num_classes)
+    elif isinstance(model, HybridVAE):
+        kind = "hybrid"
+        if cond is not None:
+            raise ValueError("a HybridVAE takes no cond")
+        if model.audio_only and text is not None:
+            raise ValueError("an audio-only HybridVAE takes no text")
+        if not model.audio_only and text is None:
+            raise ValueError("a HybridVAE with a text branch needs text")
+        widths = (0 if model.audio_only else model.text_dim, 0)
+    else:
+        raise TypeError("expected a HybridVAE or a ConditionalVAE")
+    H, W = model.input_hw
+    audio = audio.detach() if torch.is_tensor(audio) else torch.from_numpy(np.asarray(audio, dtype=np.float32))
+    if audio.dim() not in (3, 4) or tuple(audio.shape[-2:]) != (H, W) or audio.numel() != audio.shape[0] * H * W:
+        raise ValueError(f"audio must be [n, 1, {H}, {W}] (or [n, {H}, {W}]), got {tuple(audio.shape)}")
+    n = audio.shape[0]
+    if n < 1:
+        raise ValueError("audio has no rows")
+    mats = [audio.reshape(n, H * W)]
+    for name, x, w in (("text", text, widths[0]), ("cond", cond, widths[1])):
+        if x is None:
+            mats.append(None)
+            continue
+        x = x.detach() if torch.is_tensor(x) else torch.from_numpy(np.asarray(x, dtype=np.float32))
+        if x.dim() != 2 or x.shape[1] != w:
+            raise ValueError(f"{name} must be [n, {w}], got {tuple(x.shape)}")
+        if x.shape[0] != n:
+            raise ValueError(f"{name} has {x.shape[0]} rows, audio has {n}")
+        mats.append(x)
+    mats = [None if x is None else x.to(torch.float32) for x in mats]
+    if finite and any(x is not None and not bool(torch.isfinite(x).all()) for x in mats):
+        raise ValueError("Input contains NaN or infinity.")
+    return kind, mats
+
+
+def fit_conv_vae(model, audio, text=None, cond=None, *, epochs=500, batch_size=32, lr=1e-4, beta=None, text_weight=None,
+                 patience=None, val_fraction=0.15, normalize=None, generator=None, restore_best=False, split=None):
+    """The training runs of the reference's two convolutional scripts on device-resident data: the Hybrid VAE's
+    (src/Convolutional_VAE.py:59-66, 202-271; ``model`` a ``HybridVAE``, audio-only included, then ``text`` must be
+    None) and the CVAE's (src/Conditional_VAE.py:310-362, 378-394; ``model`` a ``ConditionalVAE``, ``cond``
+    [n][num_classes] required): ``random_split`` into 85 % / 15 %, ``DataLoader(train, shuffle=True)`` and
+    ``DataLoader(val, shuffle=False)``, ``Adam(lr)`` at a constant rate, the summed loss, early stopping after
+    ``patience`` epochs without a strictly lower validation loss.  Returns a ``ConvFitResult``; the model is left in
+    eval mode, as both reference loops leave it.
+
+    Defaults by kind -- hybrid: beta 1.0, text_weight 350, patience 15, ``normalize="samples"`` (epoch sums divided by
+    ``len(loader.dataset)``); CVAE: beta 4.0, text_weight 200, patience 20, ``normalize="batches"`` (divided by
+    ``len(loader)``).  ``epochs`` and ``lr`` are the hybrid script's; the CVAE script passes its CONFIG's (600, 1e-4).
+
+    The split is ``random_split_indices(n, split_sizes(n, val_fraction), generator)`` unless
+    ``split=(train_idx, val_idx)`` is given.  Per epoch the training order (``dataloader_order`` composed with
+    train_idx) is uploaded once; per step one hlmc_batch_gather per input tensor fills static [batch_size][...] buffers
+    (the ``train_size % batch_size`` tail rows go into buffers of their own and run as a real smaller batch) and one
+    ``Trainer.step`` draws its eps from the engine's Philox stream and leaves its loss sums in the step's row of a
+    device table.  The validation pass gathers each batch the same way, runs the engine's eval-mode forward (eps from
+    the same stream, BatchNorm running statistics read and not updated) and hlmc_loss_sums into a second table.  One
+    hlmc_fit_epoch_totals launch and ONE read-back of five doubles end the epoch -- its only synchronisation.  On an
+    improvement every parameter and buffer goes into a preallocated snapshot with one ``torch._foreach_copy_``;
+    ``restore_best`` (off: neither script restores) writes it back at the end.
+
+    The epoch figures add the float64 loss sums of every step; the reference adds their float32 ``.item()`` values,
+    about 1e-7 relative apart, which can matter only at an exact tie of the ``<`` comparison.  The global generator (or
+    ``generator``) is consumed by the split and ``dataloader_order`` alone: the reference's own ``randn_like`` draws
+    from it on the CPU, so its batch order after the first step is not reproducible by anyone.  A training tail of one
+    row (or ``batch_size == 1``) raises ValueError before the engine launches anything, as train-mode BatchNorm would; a
+    validation tail of one row is legal.  Every argument check comes before the first engine call; the one check that
+    reads the data, the finite test, runs where the data lives, so for inputs already on the device it is a torch
+    reduction and a synchronisation there."""
+    kind, mats = _conv_inputs(model, audio, text, cond, finite=True)
+    n = mats[0].shape[0]
+    dflt = _CONV_DEFAULTS[kind]
+    beta = dflt["beta"] if beta is None else float(beta)
+    text_weight = dflt["text_weight"] if text_weight is None else float(text_weight)
+    patience = dflt["patience"] if patience is None else int(patience)
+    normalize = dflt["normalize"] if normalize is None else normalize
+    epochs, bs = int(epochs), int(batch_size)
+    if epochs < 1 or bs < 1 or patience < 1:
+        raise ValueError("epochs, batch_size and patience must be positive")
+    if normalize not in ("samples", "batches"):
+        raise ValueError("normalize must be 'samples' or 'batches'")
+    if split is None:
+        nt_rows, nv_rows = split_sizes(n, val_fraction)
+    else:
+        if len(split) != 2:
+            raise ValueError("split must be (train_idx, val_idx)")
+        train_idx, val_idx = (torch.as_tensor(t).detach().cpu().to(torch.int64).reshape(-1) for t in split)
+        nt_rows, nv_rows = train_idx.numel(), val_idx.numel()
+    if nt_rows < 1 or nv_rows < 1:
+        raise ValueError(f"the split leaves {nt_rows} training and {nv_rows} validation rows of {n}")
+    if bs == 1 or nt_rows % bs == 1:
+        raise ValueError(f"a training batch of one row ({nt_rows} training rows, batch_size = {bs}): BatchNorm in train "
+                         f"mode needs more than 1 value per channel")
+    if split is None:
+        train_idx, val_idx = random_split_indices(n, [nt_rows, nv_rows], generator)
+    else:
+        both = torch.cat([train_idx, val_idx])
+        if int(both.min()) < 0 or int(both.max()) >= n:
+            raise ValueError("split indices outside [0, n)")
+    train_rows = [bs] * (nt_rows // bs) + ([nt_rows % bs] if nt_rows % bs else [])
+    val_rows = [bs] * (nv_rows // bs) + ([nv_rows % bs] if nv_rows % bs else [])
+
+    dev = next(model.parameters()).device
+    tr = Trainer(model, lr=lr, beta=beta, text_weight=text_weight)   # a CPU model is refused here
+    lib = L.lib()
+    data = [None if x is None else x.to(dev).contiguous() for x in mats]
+    H, W = model.input_hw
+    shapes = [(1, H, W), (mats[1].shape[1],) if mats[1] is not None else None,
+              (mats[2].shape[1],) if mats[2] is not None else None]
+    inputs = {B: [None if x is None else torch.empty(B, *shp, device=dev) for x, shp in zip(data, shapes)]
+              for B in set(train_rows + val_rows)}
+    valid = torch.zeros(1, dtype=torch.int32, device=dev)
+    train_table = torch.zeros(len(train_rows), 3, dtype=torch.float64, device=dev)
+    val_table = torch.zeros(len(val_rows), 3, dtype=torch.float64, device=dev)
+    out5 = torch.zeros(5, dtype=torch.float64, device=dev)
+    divs = (nt_rows, nv_rows) if normalize == "samples" else (len(train_rows), len(val_rows))
+    train_dev, val_dev = train_idx.to(dev), val_idx.to(dev)
+    stopper = PlateauStopper(lr, lr_patience=epochs, stop_patience=patience)   # lr_patience = epochs: the rate stays
+    sd = model.state_dict()  # detached views of the live parameters and buffers, in the file's key order
+    live = list(sd.values())
+    snap = [torch.empty_like(t) for t in live]
+    keys = ("train_loss", "audio", "text", "kld", "val_loss")
+    hist = {k: [] for k in keys}
+    stopped = None
+
+    def gather(idx_dev, start, B):
+        bufs = inputs[B]
+        for x, buf in zip(data, bufs):
+            if x is not None:
+                L.check(lib.hlmc_batch_gather(L.stream(), x.data_ptr(), n, x.shape[1], idx_dev.data_ptr() + 8 * start,
+                                              B, B, buf.data_ptr(), valid.data_ptr()), "hlmc_batch_gather")
+        return bufs
+
+    model.train()
+    try:
+        for e in range(epochs):
+            order = train_dev[dataloader_order(nt_rows, generator).to(dev)]
+            start = 0
+            for k, B in enumerate(train_rows):
+                a, t, c = gather(order, start, B)
+                tr.step(a, t, c, sums=train_table[k])
+                start += B
+            start = 0
+            for j, B in enumerate(val_rows):
+                a, t, c = gather(val_dev, start, B)
+                cb = tr._buffers(B)   # outputs, workspace and loss workspace: one set per batch size
+                out = cb["out"]
+                L.check(lib.hlmc_net_forward(tr.net.h, L.stream(), B, 0, L.ptr(a), L.ptr(t), L.ptr(c), None, None,
+                                             L.ptr(out["recon"]), L.ptr(out.get("recon_text")), L.ptr(out["mu"]),
+                                             L.ptr(out["logvar"]), None, cb["ws"].data_ptr()), "hlmc_net_forward")
+                na, ntx, nl = cb["n"]
+                L.check(lib.hlmc_loss_sums(L.stream(), L.ptr(out["recon"]), L.ptr(a), na, L.ptr(out.get("recon_text")),
+                                           L.ptr(t if ntx else None), ntx, L.ptr(out["mu"]), L.ptr(out["logvar"]), nl,
+                                           val_table[j].data_ptr(), cb["lws"].data_ptr()), "hlmc_loss_sums")
+                start += B
+            L.check(lib.hlmc_fit_epoch_totals(L.stream(), train_table.data_ptr(), len(train_rows), val_table.data_ptr(),
+                                              len(val_rows), text_weight, beta, float(divs[0]), float(divs[1]),
+                                              out5.data_ptr()), "hlmc_fit_epoch_totals")
+            totals = out5.cpu().tolist()  # the epoch's one synchronisation
+            L.check_device("fit_conv_vae")
+            for key, v in zip(keys, totals):
+                hist[key].append(v)
+            improved, _, stop = stopper.update(totals[4])
+            if improved:
+                torch._foreach_copy_(snap, live)
+            if stop:
+                stopped = e
+                break
+    finally:
+        # release first: the engine trusts the packed weights Adam wrote, so weights restored behind it would go unseen
+        tr.release()
+        if restore_best and stopper.best_epoch is not None:
+            torch._foreach_copy_(live, snap)
+        model.eval()
+    best_state = type(sd)(zip(sd.keys(), snap)) if stopper.best_epoch is not None else None
+    return ConvFitResult({k: np.asarray(v, dtype=np.float64) for k, v in hist.items()}, stopper.best_epoch,
+                         stopper.best_loss, stopped, best_state, train_idx, val_idx, model.get_rng_state())
+
+
+def extract_latents(model, audio, text=None, cond=None, batch_size=32):
+    """``model.eval()`` and mu of ``model.encode`` over consecutive chunks of ``batch_size`` rows (the latent
+    extraction of src/Convolutional_VAE.py:286-303), with one workspace for all chunks; ``batch_size`` None takes the
+    whole set in one call (src/Conditional_VAE.py:397-402).  Returns mu [n][latent] as a float32 device tensor."""
+    _, mats = _conv_inputs(model, audio, text, cond, finite=False)
+    n = mats[0].shape[0]
+    bs = n if batch_size is None else int(batch_size)
+    if bs < 1:
+        raise ValueError("batch_size must be positive")
+    bs = min(bs, n)
+    model.eval()
+    net = model._native_net()   # a CPU model is refused here
+    dev = next(model.parameters()).device
+    data = [None if x is None else x.to(dev).contiguous() for x in mats]
+    lib, latent = L.lib(), model.latent_dim
+    mu = torch.empty(n, latent, device=dev)
+    lv = torch.empty(bs, latent, device=dev)
+    ws = torch.empty(max(net.workspace_bytes(B) for B in {bs, n % bs or bs}), dtype=torch.uint8, device=dev)
+    for lo in range(0, n, bs):
+        B = min(bs, n - lo)
+        a, t, c = (None if x is None else x[lo:lo + B] for x in data)
+        L.check(lib.hlmc_net_encode(net.h, L.stream(), B, 0, L.ptr(a), L.ptr(t), L.ptr(c), mu[lo:lo + B].data_ptr(),
+                                    lv.data_ptr(), ws.data_ptr()), "hlmc_net_encode")
+    return mu

@@ -314,6 +314,22 @@ int hlmc_mse_rows(void* stream, const float* recon, const float* target, int B, 
  * 1e-7 relative apart.  Host checks: pointers non-NULL, nb >= 1, beta not NaN; else HLMC_EINVAL before any launch. */
 int hlmc_vae_epoch_means(void* stream, const double* sums, const int64_t* na_nl, int nb, double beta, double* out3);
 
+/* ============================================================== convolutional VAE fits: epoch totals
+ * The epoch figures of src/Convolutional_VAE.py:237-256 and src/Conditional_VAE.py:331-345 without a read-back per step
+ * or per validation batch.  Training step k of the epoch wrote its loss sums (hlmc_loss_sums_backward) to train_sums[k]
+ * (DEVICE double[nt][3]), validation batch j (hlmc_loss_sums) to val_sums[j] (DEVICE double[nv][3]); a row is
+ * { sum (ra-a)^2, sum (rt-t)^2, sum (1 + lv - mu^2 - exp lv) }.  One launch, one thread, float64, rows in step order,
+ * every operation rounded once (no FMA contraction), the association as written:
+ *   kld_s = -0.5 * s[2],  total_s = (s[0] + text_weight * s[1]) + beta * kld_s,
+ *   out5 (DEVICE double[5]) = { sum_train total_s / train_div, sum_train s[0] / train_div, sum_train s[1] / train_div,
+ *                               sum_train kld_s / train_div, sum_val total_s / val_div }.
+ * Divisors: the data-set lengths for the hybrid script (len(loader.dataset)), the batch counts for the CVAE script
+ * (len(loader)).  The reference adds the float32 .item() of each step's loss; these are the float64 values of the same
+ * steps, about 1e-7 relative apart.  Host checks: pointers non-NULL, nt >= 1, nv >= 1, both divisors > 0, none of the
+ * four scalars NaN; else HLMC_EINVAL before any launch. */
+int hlmc_fit_epoch_totals(void* stream, const double* train_sums, int nt, const double* val_sums, int nv,
+                          double text_weight, double beta, double train_div, double val_div, double* out5);
+
 /* ============================================================== optimizer
  * torch.optim.Adam(lr, betas, eps, weight_decay) step (src/Convolutional_VAE.py:208,235) over
  * n tensors in one launch.  ptr arrays are HOST arrays of device pointers. */
